@@ -17,11 +17,17 @@ A step = one forward pass over one synthetic KITTI-shaped pair already resident 
 the reference does).  Weights: the reference's random initialisation, BN statistics and
 head scale calibrated (dsmnet_amd/calibrate.py).  Compute dtype fp32, as the reference.
 
-Rank 0 prints ONE JSON line: throughput (K steps between two barriers), per-step spread
-(median / min from one HIP event per step), the per-kernel rooflines from a second,
-instrumented pass (two HIP events per launch on the launch stream) and, at N=1, the CPU
-baseline: the oracle restatement of the same forward on the same weights, per stage, timed on
-the host cores.
+Rank 0 prints ONE JSON line: throughput (K steps between two barriers) and the per-step spread
+(median / min from one HIP event per step).  A plain run does nothing else: set-up, W warm-up
+steps, the K timed steps, the line.  ``--full`` adds what takes runs of its own: the per-kernel
+rooflines from a second, instrumented pass (two HIP events per launch on the launch stream), the
+cost-volume build measured on its own and, at N=1, the CPU baseline: the oracle restatement of the
+same forward on the same weights, per stage, timed on the host cores.
+
+``--dump-outputs DIR`` writes what the last timed step returned on rank 0 -- the three disparity
+maps pred3, pred2, pred1 of shape (1, H, W) -- as DIR/<name>.npy in float32 (5.9 MB in all).
+The pair and the weights' initialisation are seeded, so runs with the same arguments see the
+same inputs and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -196,6 +202,15 @@ def cpu_baseline(model, left, right, gpu_preds):
             "stage_seconds": {k: round(v, 3) for k, v in best_stages.items()}}, err
 
 
+def dump_outputs(out_dir, preds):
+    """The disparity maps one step returned ([pred3, pred2, pred1], as the model's forward orders
+    them) -> out_dir/<name>.npy, float32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, p in zip(("pred3", "pred2", "pred1"), preds):
+        np.save(os.path.join(out_dir, name + ".npy"), p.detach().float().cpu().numpy())
+
+
 # ----------------------------------------------------------------------------
 # self-launch: `python bench.py --gpus N` without a launcher around it
 # ----------------------------------------------------------------------------
@@ -254,12 +269,19 @@ def main():
     # forward speeding up from 5.45 to 5.02 ms while the clocks settle; 30 untimed + 50 timed steps = 0.4 s
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-kernel rooflines, the cost-volume build and (N=1) the CPU "
+                         "baseline, each in runs of its own after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the disparity maps of the last timed step (rank 0) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true",
                     help="time eager launches instead of hipGraph replays")
     ap.add_argument("--no-kernel-timing", action="store_true",
-                    help="skip the second, instrumented pass (per-launch HIP events -> rooflines)")
+                    help="with --full: skip the second, instrumented pass (per-launch HIP events -> rooflines)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # DSM_BENCH_REHEARSE=1: rehearsal of the N > 1 control path on a box with fewer GPUs than ranks
     # (ranks share devices, gloo carries the barrier and the max-reduce).  Its value is not a
@@ -348,12 +370,14 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         step_ms = [a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:])]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, preds)
         # the same K steps again with two HIP events around every launch of this library (on
         # the launch stream): per-kernel durations for the rooflines.  Kept out of the timed
         # region because the event records themselves cost ~5 % of a step.
         timer = instrumented = None
         volume_b2b_us = volume_seq_us = r01_path_ms = None
-        if not args.no_kernel_timing:
+        if args.full and not args.no_kernel_timing:
             timer = costvolume.LaunchTimer()
             costvolume.set_timer(timer)
             barrier()
@@ -475,7 +499,7 @@ def main():
                 "how": "%d eager steps right after the timed region with two HIP events per "
                        "launch on the launch stream" % args.steps,
                 "instrumented_ms_per_step": round(instrumented / args.steps * 1e3, 3)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base, err = cpu_baseline(model, left, right, preds)
             result["cpu_baseline"] = base
             result["parity_max_abs_px_vs_cpu"] = err

@@ -54,7 +54,7 @@ for k, n in NAMES.items():
 json.dump(tj, open(tpath, "w"), indent=1)
 print("""# %s — PMC passes over the benchmark itself (commit %s)
 
-`scripts/pmc_passes.sh OUT bench.py --no-cpu-baseline --steps 5 --warmup 2` on one MI355X: four separate
+`scripts/pmc_passes.sh OUT bench.py --full --no-cpu-baseline --steps 5 --warmup 2` on one MI355X: four separate
 `rocprofv3 --kernel-trace --pmc <set> -- python3 bench.py ...` passes (SQ/GRBM set; LDS set; FETCH_SIZE; WRITE_SIZE),
 reduced with `scripts/pmc_table.py` to the mean per dispatch of every kernel in the run (PSMNet D=192, 384x1280,
 default precision f16x2), then `scripts/pmc_report.py`.  FETCH/WRITE in KiB.

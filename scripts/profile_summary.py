@@ -64,7 +64,7 @@ total = sum(float(r["TotalDurationNs"]) for r in rows)
 ours = [r for r in rows if any(k in r["Name"] for k in OURS)]
 ours_total = sum(float(r["TotalDurationNs"]) for r in ours)
 roofs = bench.get("rooflines", {})
-print("# Run %s — `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline`\n" % tag.upper())
+print("# Run %s — `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline`\n" % tag.upper())
 print("PSMNet D=192, 384x1280, 1 MI355X.  Un-profiled bench line (`%s_bench.json`): **%.1f pairs/s**, %.2f ms/step (%s);"
       % (tag, bench["value"], bench["ms_per_step"], bench["config"].get("launch", "eager launches")))
 cb = bench.get("cpu_baseline")

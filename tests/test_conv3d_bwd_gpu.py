@@ -78,7 +78,12 @@ def _trunk_step_errors(seed, hw=(16, 40), d4=8):
     r02): the product runs first and records the sign pattern of every ReLU input; the oracle's
     trunk then runs with those masks forced (y = x * mask_k in place of its k-th F.relu -- the same
     function wherever the signs agree, and the same derivative everywhere).  What is left is
-    arithmetic: summation order and the products' precision."""
+    arithmetic: summation order and the products' precision.
+
+    The oracle runs in float64.  Its fp32 CPU autograd is not accurate enough to judge the product at
+    GRAD_TOL: at the config #5 shape, with the same masks, its weight gradients lie up to 2e-3 (relative
+    to the largest entry) from its own float64 result -- classif3.0.0.weight, summed over 1.6e6 voxels
+    with heavy cancellation -- and by how much depends on the host's thread count."""
     import torch.nn.functional as TF
     from dsmnet_amd import blocks3d
     from dsmnet_amd import costvolume as cv
@@ -111,9 +116,9 @@ def _trunk_step_errors(seed, hw=(16, 40), d4=8):
     params = dict(m.named_parameters())
     ggr = torch.autograd.grad(loss, [params[k] for k in keys] + [gfl, gfr])
     # oracle: leaves that require grad; its k-th ReLU takes the product's k-th mask
-    osd = {k: (v.clone().requires_grad_(True) if v.is_floating_point() and "running" not in k
-               else v.clone()) for k, v in sd.items()}
-    ofl, ofr = fl.clone().requires_grad_(True), fr.clone().requires_grad_(True)
+    osd = {k: (v.double().requires_grad_(True) if v.is_floating_point() and "running" not in k
+               else v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    ofl, ofr = fl.double().requires_grad_(True), fr.double().requires_grad_(True)
     n = OM.Net(osd, training=True)
     state = {"k": 0, "flips": 0, "units": 0}
 
