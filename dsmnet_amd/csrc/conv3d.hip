@@ -1123,6 +1123,11 @@ int make_plan(const dsm_conv3d_args* a, Plan* pl) {
     pl->pm = a->precision == DSM_PREC_F16X2 ? 2 : 1;
   }
   if (pl->pm == 3) pl->once = 0;                         // the single-tile form exists in the fp16 modes only
+  // transposed layers of 64+ inputs in the fp16 modes: the z-sliding kernel (deconv_zs.hpp; two or more
+  // 32-channel groups: one exchange buffer; 32-bit offsets within an input plane)
+  if (pl->kind == 6 && pl->pm != 3 && DSM_DECONV_ZS && a->Cin % 64 == 0 &&
+      4l * a->Hi * a->Wi * a->Cin < 0x7fffffffl)
+    pl->zs = 1;
   return DSM_OK;
 }
 }  // namespace
@@ -1152,7 +1157,8 @@ extern "C" int dsm_conv3d_plan(const dsm_conv3d_args* a, char* buf, int len) {
       break;
     }
     case 7: snprintf(buf, len, "conv3d_zs_%s_mfma_kernel%s", pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), a->vol_virtual ? "<vol>" : ""); break;
-    case 6: snprintf(buf, len, "deconv3d_%s_mfma_kernel<NT=%d>", pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), pl.NT); break;
+    case 6: snprintf(buf, len, "deconv3d_%s%s_mfma_kernel<NT=%d>", pl.zs ? "zs_" : "",
+                     pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), pl.NT); break;
     default: snprintf(buf, len, "deconv3d_cout1_kernel"); break;
   }
   return DSM_OK;

@@ -27,7 +27,12 @@ struct ConvParams {
 // One place decides the kernel variant; dsm_conv3d_fwd launches it, dsm_conv3d_plan names it.
 // kind: 0 conv, 1 deconv, 2 conv cout1, 3 deconv cout1, 4 conv cout1 z-sliding, 5 conv split (bf16x3 / f16x2 / f16), 6 deconv split,
 //       7 z-sliding conv (Cout = 32, stride 1; conv_zs.hpp)
-struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int pm = 3; int once = 0; };
+// zs (kind 6, fp16 modes): the z-sliding transposed convolution (deconv_zs.hpp) instead of deconv_split_kernel
+struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int pm = 3; int once = 0; int zs = 0; };
+
+#ifndef DSM_DECONV_ZS
+#define DSM_DECONV_ZS 1       // 0: plan kind 6 stays on deconv_split_kernel in the fp16 modes (A/B builds)
+#endif
 
 // the z-sliding kernel (conv_zs.hpp, plan kind 7)
 struct ZsParams {

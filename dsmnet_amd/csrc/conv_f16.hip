@@ -13,6 +13,7 @@
 namespace {
 #include "conv_split.hpp"
 #include "conv_zs.hpp"
+#include "deconv_zs.hpp"
 #include "basicblock2d.hpp"
 }  // namespace
 
@@ -23,6 +24,7 @@ int dsmk::run_zs_f16(int pm, const ZsParams& p, int grid, hipStream_t s) {
 }
 
 int dsmk::run_split_f16(const Plan& pl, const ConvParams& p, hipStream_t s) {
+  if (pl.kind == 6 && pl.zs) return pl.pm == 2 ? run_deconv_zs<2>(p, s) : run_deconv_zs<1>(p, s);
   if (pl.pm == 2) return dispatch_split<2>(pl, p, s);
   if (pl.pm == 1) return dispatch_split<1>(pl, p, s);
   return DSM_ERR_UNSUPPORTED;
