@@ -55,6 +55,17 @@ class BasicBlock2dArgs(ctypes.Structure):
                 ("B", c_int), ("H", c_int), ("W", c_int), ("C", c_int), ("precision", c_int), ("relu", c_int), ("no_skip", c_int)]
 
 
+class SelfsupItem(ctypes.Structure):
+    """struct dsm_selfsup_item (include/dsmnet_hip.h)."""
+    _fields_ = [("im", c_void_p), ("src", c_void_p), ("disp", c_void_p), ("disp_other", c_void_p),
+                ("grad_disp", c_void_p), ("grad_other", c_void_p),
+                ("im_stride", c_int * 4), ("src_stride", c_int * 4),
+                ("B", c_int), ("h", c_int), ("w", c_int), ("H0", c_int), ("W0", c_int),
+                ("left", c_int), ("top", c_int), ("scale_factor", c_int),
+                ("delt_im", ctypes.c_float), ("delt_disp", ctypes.c_float), ("weight", ctypes.c_float),
+                ("pad_", c_int)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in dsmnet_hip.h
 SIGNATURES = {
     "dsm_abi_version": (c_int, []),
@@ -87,6 +98,9 @@ SIGNATURES = {
     "dsm_spp_branches": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     "dsm_spp_concat": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 2),
     "dsm_warp_abs_error": (c_int, [c_void_p] * 4 + [c_int] * 6 + [ctypes.c_float, c_void_p]),
+    "dsm_selfsup_workspace_floats": (c_size_t, [ctypes.POINTER(SelfsupItem), c_int]),
+    "dsm_selfsup_fwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
+    "dsm_selfsup_bwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
 }
 
 _lib = None

@@ -1143,3 +1143,142 @@ def decoder_level(deconv, x, pr, skip):
                                          Hu, Wu, Hp, Wp, Hs, Ws, int(relu), _stream())
     _lib.check(rc, "dsm_decoder_cat")
     return out
+
+
+# ----------------------------------------------------------------------------
+# Self-supervised depthmono[-mask] pyramid loss (csrc/selfsup.hip)
+# ----------------------------------------------------------------------------
+def _int_strides(name, t):
+    st = t.stride()
+    if any(s < 0 or s >= 2 ** 31 for s in st) or t.numel() >= 2 ** 31:
+        raise ValueError("%s: strides %s do not fit the kernel's 32-bit indexing" % (name, st))
+    return st
+
+
+class SelfsupPyramidLossFunction(torch.autograd.Function):
+    """Items 2p / 2p+1 = the two views of pyramid entry p (csrc/selfsup.hip).  ``spec`` holds the
+    host-side description; the tensors ride as arguments so that autograd sees the disparities."""
+
+    @staticmethod
+    def _items(spec, imgs, disps, grads=None):
+        imL, imR_src, imL1, imR1_src = imgs
+        n = len(spec["levels"])
+        items = (_lib.SelfsupItem * (2 * n))()
+        for p in range(n):
+            k, sf = spec["levels"][p], spec["factors"][p]
+            dL, dL1 = disps[p], disps[n + p]
+            gL, gL1 = (grads[p], grads[n + p]) if grads is not None else (None, None)
+            for side, (im, src, lt, d, do, g, go, di, dd) in enumerate((
+                    (imL, imR_src, spec["lefttop"], dL, dL1, gL, gL1, 0, 2),
+                    (imL1, imR1_src, spec["lefttop1"], dL1, dL, gL1, gL, 1, 3))):
+                lvl = im[:, :, ::2 ** k, ::2 ** k]
+                it = items[2 * p + side]
+                it.im, it.src = lvl.data_ptr(), src.data_ptr()
+                it.disp, it.disp_other = d.data_ptr(), do.data_ptr()
+                it.grad_disp = None if g is None else g.data_ptr()
+                it.grad_other = None if go is None else go.data_ptr()
+                it.im_stride[:] = list(lvl.stride())
+                it.src_stride[:] = list(src.stride())
+                it.B, it.h, it.w = lvl.shape[0], lvl.shape[2], lvl.shape[3]
+                it.H0, it.W0 = src.shape[2], src.shape[3]
+                it.left, it.top = int(lt[0]), int(lt[1])
+                it.scale_factor = int(sf)
+                it.delt_im, it.delt_disp = float(spec["delts"][p][di]), float(spec["delts"][p][dd])
+                it.weight = float(spec["weights"][p])
+        return items
+
+    @staticmethod
+    def forward(ctx, spec, imL, imR_src, imL1, imR1_src, *disps):
+        imgs = (imL, imR_src, imL1, imR1_src)
+        items = SelfsupPyramidLossFunction._items(spec, imgs, disps)
+        lib = _lib.load()
+        nf = lib.dsm_selfsup_workspace_floats(items, len(items))
+        if nf == 0:
+            raise ValueError("selfsup_pyramid_loss: empty or invalid item list")
+        ws = torch.empty(nf, device=imL.device, dtype=torch.float32)
+        loss = torch.empty((), device=imL.device, dtype=torch.float32)
+        aux = torch.empty(4 * len(items), device=imL.device, dtype=torch.float32)
+        with torch.cuda.device(imL.device), _timed("selfsup_fwd", 4.0 * nf):
+            rc = lib.dsm_selfsup_fwd(items, len(items), int(bool(spec["flag_mask"])), _p(ws), _p(loss),
+                                     _p(aux), _stream())
+        _lib.check(rc, "dsm_selfsup_fwd")
+        ctx.spec = spec
+        ctx.save_for_backward(imL, imR_src, imL1, imR1_src, ws, aux, *disps)
+        ctx.mark_non_differentiable(aux)
+        return loss, aux
+
+    @staticmethod
+    def backward(ctx, gloss, gaux):
+        saved = ctx.saved_tensors
+        imgs, ws, aux, disps = saved[:4], saved[4], saved[5], saved[6:]
+        flat = torch.zeros(sum(d.numel() for d in disps), device=ws.device, dtype=torch.float32)
+        grads, o = [], 0
+        for d in disps:
+            grads.append(flat[o:o + d.numel()].view(d.shape))
+            o += d.numel()
+        items = SelfsupPyramidLossFunction._items(ctx.spec, imgs, disps, grads)
+        g = gloss.to(torch.float32).contiguous()
+        with torch.cuda.device(ws.device), _timed("selfsup_bwd", 4.0 * (ws.numel() + 2 * flat.numel())):
+            rc = _lib.load().dsm_selfsup_bwd(items, len(items), int(bool(ctx.spec["flag_mask"])), _p(ws),
+                                             _p(aux), _p(g), _stream())
+        _lib.check(rc, "dsm_selfsup_bwd")
+        return (None, None, None, None, None) + tuple(grads)
+
+
+def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1, dispL1s, levels,
+                         weights, factors, flag_mask, delts, return_aux=False):
+    """The reference's depthmono[-mask] objective over a disparity pyramid in three launches
+    forward and two backward (csrc/selfsup.hip; losses/loss.py:196-236, 393-405, 424-467,
+    losses/SSIM.py, utils/imwrap.py:37-72):
+
+        sum_p weights[p] * (loss_depthmono(imL_k, imwrap(imR_src, dispLs[p], LeftTop=lefttop,
+                scale_factor=factors[p]), dispLs[p], imwrap(dispL1s[p], dispLs[p], fliplr=True))
+              + the same for the flipped view)
+
+    with imL_k = imL[:, :, ::2**k, ::2**k], k = levels[p].  ``imL``/``imL1`` (B,3,h,w) and
+    ``imR_src``/``imR1_src`` (B,3,H0,W0) may be strided views; ``dispLs[p]``/``dispL1s[p]``
+    (B,1,h_k,w_k) take the gradient.  ``delts[p]`` = the reference's four random epsilons of the
+    entry, in its draw order (imL_wrap, imL1_wrap, dispL_wrap, dispL1_wrap).  No host
+    synchronisation.  ``return_aux``: also the (2P,4) per-view [w, fallback, C, simlary]."""
+    n = len(dispLs)
+    if not (len(dispL1s) == len(levels) == len(weights) == len(factors) == len(delts) == n) or n < 1:
+        raise ValueError("selfsup_pyramid_loss: one level, weight, factor and delt set per disparity")
+    if 2 * n > 16:
+        raise ValueError("selfsup_pyramid_loss: at most 8 pyramid entries, got %d" % n)
+    _require_device("selfsup_pyramid_loss", imL, imR_src, imL1, imR1_src, *dispLs, *dispL1s)
+    dev = imL.device
+    for t in (imR_src, imL1, imR1_src) + tuple(dispLs) + tuple(dispL1s):
+        if t.device != dev:
+            raise ValueError("selfsup_pyramid_loss: every tensor must be on %s, got %s" % (dev, t.device))
+    for name, im, src in (("imL", imL, imR_src), ("imL1", imL1, imR1_src)):
+        if im.dim() != 4 or im.shape[1] != 3 or src.dim() != 4 or src.shape[:2] != im.shape[:2]:
+            raise ValueError("selfsup_pyramid_loss: %s %s and its source %s must be (B,3,h,w) and "
+                             "(B,3,H0,W0)" % (name, tuple(im.shape), tuple(src.shape)))
+        if min(src.shape[2:]) <= 1:
+            raise ValueError("selfsup_pyramid_loss: maps must be larger than 1x1")   # imwrap.py:48
+        _int_strides(name, im)
+        _int_strides(name, src)
+    if imL.shape != imL1.shape:
+        raise ValueError("selfsup_pyramid_loss: the two views differ: %s vs %s"
+                         % (tuple(imL.shape), tuple(imL1.shape)))
+    B, _, h, w = imL.shape
+    ds = []
+    for p in range(n):
+        k = int(levels[p])
+        hk, wk = -(-h // 2 ** k), -(-w // 2 ** k)
+        for d in (dispLs[p], dispL1s[p]):
+            if tuple(d.shape) != (B, 1, hk, wk):
+                # the reference would fail to broadcast im against disp here
+                raise ValueError("selfsup_pyramid_loss: disparity %d is %s, its image level %d is %s"
+                                 % (p, tuple(d.shape), k, (B, 1, hk, wk)))
+            if hk <= 1 or wk <= 1:
+                raise ValueError("selfsup_pyramid_loss: maps must be larger than 1x1")
+        if int(factors[p]) < 1 or len(delts[p]) != 4:
+            raise ValueError("selfsup_pyramid_loss: bad factor / delts at entry %d" % p)
+    ds = [d.contiguous() for d in dispLs] + [d.contiguous() for d in dispL1s]
+    spec = {"levels": [int(k) for k in levels], "factors": [int(f) for f in factors],
+            "weights": [float(x) for x in weights], "delts": [tuple(float(x) for x in dl) for dl in delts],
+            "lefttop": (int(lefttop[0]), int(lefttop[1])), "lefttop1": (int(lefttop1[0]), int(lefttop1[1])),
+            "flag_mask": bool(flag_mask)}
+    loss, aux = SelfsupPyramidLossFunction.apply(spec, imL, imR_src, imL1, imR1_src, *ds)
+    return (loss, aux.view(2 * n, 4)) if return_aux else loss

@@ -1,0 +1,523 @@
+// Self-supervised "depthmono[-mask]" pyramid loss (losses/loss.py:196-236 loss_depthmono,
+// :71-83 C_ds1, :393-405 weight_common, :424-467 losses_pyramid1; losses/SSIM.py:6-14, 24-42,
+// 94-117; utils/imwrap.py:37-72 imwrap_BCHW with LeftTop / scale_factor / fliplr), fused.
+//
+// Stock torch spends ~220 small launches per (level, view) on this, forward and backward (3125
+// for the preset pyramid, profiles/selfsup.md).  Here
+// the whole pyramid (every level, both views) is ONE work list of 16x16 output tiles:
+//   forward   selfsup_fwd_tiles   per tile: the image warp over the tile + 5-pixel halo, the five
+//                                 channel-mean statistics, the separable 11-tap Gaussian in LDS,
+//                                 SSIM, C_ap, C_ds1, the fliplr disparity warp, C_lr, the -mask
+//                                 weights; per-tile partial sums to a slab, and 5 floats per pixel
+//                                 saved for the backward (the SSIM partials and both candidate
+//                                 weight_im maps: which one applies is known only after the
+//                                 reduction, when the "< 1024 valid pixels" fallback is decided)
+//             selfsup_reduce      one workgroup: the slabs summed in a fixed order (fp64), the
+//                                 per-item means, simlary, w = wfun(simlary) and the weighted
+//                                 pyramid total -- all on the device, no host read
+//   backward  selfsup_bwd_tiles   per tile: the three saved SSIM partials (weighted) filtered
+//                                 again by the same symmetric window (zero padding) = the SSIM
+//                                 adjoint, the L1 sign, the bilinear derivative with respect to
+//                                 the sample position (+delt on in-bounds taps included), C_ds1,
+//                                 and the two cross-coupled left-right terms: disp is the sampling
+//                                 offset of its own disp_wrap AND the sampled source of the other
+//                                 view's, so the latter is a scatter (fp32 global atomics).
+//
+// Arithmetic follows this container's torch where it matters (see warp.hip): torch.linspace's
+// two-sided fp32 formula, grid_sample(bilinear, zeros, align_corners=False) un-normalisation and
+// tap order nw, ne, sw, se, `+ delt` on in-bounds taps only.  The masks follow the PyTorch 0.3
+// meaning: mask2 = (delta < 3) & !(delta < 1), mask_im = (disp_wrap == 0)
+// & mask_ap.  w, the masks and weight_common take no gradient, as in the reference.
+#include "common.hpp"
+
+namespace {
+
+constexpr int T = 16;                 // output tile edge
+constexpr int HALO = 5;               // 11-tap window
+constexpr int RW = T + 2 * HALO;      // 26: region edge
+constexpr int NPART = 8;              // partial sums per tile (7 used)
+constexpr int NSAVE = 5;              // floats saved per pixel
+constexpr float C1 = 1e-4f, C2 = 9e-4f;   // (0.01)^2, (0.03)^2: SSIM.py:36-38
+static_assert(sizeof(dsm_selfsup_item) == 128, "dsm_selfsup_item layout (ctypes mirror in _lib.py)");
+
+struct Work {
+  dsm_selfsup_item it[DSM_SELFSUP_MAX_ITEMS];
+  int tile0[DSM_SELFSUP_MAX_ITEMS + 1];     // first tile of each item; tile0[n] = total
+  int ntx[DSM_SELFSUP_MAX_ITEMS], nty[DSM_SELFSUP_MAX_ITEMS];
+  long save0[DSM_SELFSUP_MAX_ITEMS];        // float offset of each item's saved planes
+  float xs[DSM_SELFSUP_MAX_ITEMS], xe[DSM_SELFSUP_MAX_ITEMS];   // linspace ends (imwrap.py:53-56)
+  float ys[DSM_SELFSUP_MAX_ITEMS], ye[DSM_SELFSUP_MAX_ITEMS];
+  float g[11];                              // 1-D Gaussian, SSIM.py:6-8 (fp32, normalised)
+  int n, flag_mask;
+  float* part;                              // tile partial sums [tiles][NPART]
+  float* save;                              // [item][NSAVE][B*h*w]
+};
+
+__device__ __forceinline__ float linspace_at(float start, float end, int steps, int i) {
+  const float step = (end - start) / (float)(steps - 1);
+  return i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - i - 1);
+}
+
+__device__ __forceinline__ float sgnf(float v) { return (float)((v > 0.f) - (v < 0.f)); }
+
+// grid_sample's bilinear tap set at normalised (gx, gy) of a W0 x H0 plane
+struct Bil {
+  int x0, y0;
+  float wx0, wx1, wy0, wy1;
+  bool in00, in01, in10, in11;
+};
+
+__device__ __forceinline__ Bil bil_setup(float gx, float gy, int W0, int H0) {
+  Bil t;
+  const float ix = ((gx + 1.f) * (float)W0 - 1.f) / 2.f;
+  const float iy = ((gy + 1.f) * (float)H0 - 1.f) / 2.f;
+  const float fx = floorf(ix), fy = floorf(iy);
+  // wild disparities: clamp before the int conversion (the taps then fall outside, as in torch)
+  t.x0 = (int)fminf(fmaxf(fx, -2.f), (float)W0 + 1.f);
+  t.y0 = (int)fminf(fmaxf(fy, -2.f), (float)H0 + 1.f);
+  t.wx1 = ix - fx; t.wx0 = (fx + 1.f) - ix;
+  t.wy1 = iy - fy; t.wy0 = (fy + 1.f) - iy;
+  const bool x0in = t.x0 >= 0 && t.x0 < W0, x1in = t.x0 + 1 >= 0 && t.x0 + 1 < W0;
+  const bool y0in = t.y0 >= 0 && t.y0 < H0, y1in = t.y0 + 1 >= 0 && t.y0 + 1 < H0;
+  t.in00 = y0in && x0in; t.in01 = y0in && x1in; t.in10 = y1in && x0in; t.in11 = y1in && x1in;
+  return t;
+}
+
+// value of (plane + delt) at the taps (zeros outside) and its derivative with respect to ix
+__device__ __forceinline__ void bil_sample(const float* p, int sy, int sx, const Bil& t, float delt,
+                                           float& v, float& dvx) {
+  const float a = t.in00 ? p[(long)t.y0 * sy + (long)t.x0 * sx] + delt : 0.f;
+  const float b = t.in01 ? p[(long)t.y0 * sy + (long)(t.x0 + 1) * sx] + delt : 0.f;
+  const float c = t.in10 ? p[(long)(t.y0 + 1) * sy + (long)t.x0 * sx] + delt : 0.f;
+  const float d = t.in11 ? p[(long)(t.y0 + 1) * sy + (long)(t.x0 + 1) * sx] + delt : 0.f;
+  float s = 0.f;                                   // torch's order: nw, ne, sw, se
+  if (t.in00) s += a * (t.wx0 * t.wy0);
+  if (t.in01) s += b * (t.wx1 * t.wy0);
+  if (t.in10) s += c * (t.wx0 * t.wy1);
+  if (t.in11) s += d * (t.wx1 * t.wy1);
+  v = s;
+  dvx = (b - a) * t.wy0 + (d - c) * t.wy1;
+}
+
+struct Pix {            // one output pixel of one item
+  const dsm_selfsup_item* it;
+  int i, b, y, x;
+};
+
+// image warp at (y, x): im_wrap channels and their d/dix; the raw image channels too
+__device__ __forceinline__ void image_warp(const Work& W, const Pix& q, float d, float iw[3],
+                                           float div[3], float im[3]) {
+  const dsm_selfsup_item& it = *q.it;
+  const float gx = linspace_at(W.xs[q.i], W.xe[q.i], it.w, q.x) - d * 2.0f / (float)(it.W0 - 1);
+  const float gy = linspace_at(W.ys[q.i], W.ye[q.i], it.h, q.y);
+  const Bil t = bil_setup(gx, gy, it.W0, it.H0);
+  const float* src = (const float*)it.src + (long)q.b * it.src_stride[0];
+  const float* imp = (const float*)it.im + (long)q.b * it.im_stride[0] + (long)q.y * it.im_stride[2] +
+                     (long)q.x * it.im_stride[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    bil_sample(src + (long)c * it.src_stride[1], it.src_stride[2], it.src_stride[3], t, it.delt_im,
+               iw[c], div[c]);
+    im[c] = imp[(long)c * it.im_stride[1]];
+  }
+}
+
+// fliplr disparity warp (imwrap.py:57-70 with fliplr=True, LeftTop [0,0], scale 1): disp_other
+// sampled at -(linspace(-1, 1) - d * 2 / (w - 1)); returns the tap set for the scatter
+__device__ __forceinline__ Bil disp_warp(const Pix& q, float d, float& dw, float& ddw) {
+  const dsm_selfsup_item& it = *q.it;
+  const float gx = -(linspace_at(-1.f, 1.f, it.w, q.x) - d * 2.0f / (float)(it.w - 1));
+  const float gy = linspace_at(-1.f, 1.f, it.h, q.y);
+  const Bil t = bil_setup(gx, gy, it.w, it.h);
+  bil_sample((const float*)it.disp_other + (long)q.b * it.h * it.w, it.w, 1, t, it.delt_disp, dw, ddw);
+  return t;
+}
+
+__device__ __forceinline__ float weight_common(float d, float dw, int factor) {   // loss.py:393-405
+  const float delta = fabsf(d - dw) / (float)factor;
+  return delta < 1.f ? 1.f : (delta < 3.f ? 1.f - (delta - 1.f) * (0.99f / 2.f) : 0.01f);
+}
+
+__device__ __forceinline__ int find_item(const Work& W, int tile) {
+  int i = 0;
+  while (i + 1 < W.n && tile >= W.tile0[i + 1]) ++i;
+  return i;
+}
+
+__device__ __forceinline__ void tile_origin(const Work& W, int i, int tile, int& b, int& ty0, int& tx0) {
+  int local = tile - W.tile0[i];
+  const int per = W.ntx[i] * W.nty[i];
+  b = local / per;
+  local -= b * per;
+  ty0 = (local / W.ntx[i]) * T;
+  tx0 = (local % W.ntx[i]) * T;
+}
+
+// separable 11-tap filter of NS LDS maps: region [NS][RW][RW+1] -> value at (ty, tx) of the tile
+template <int NS>
+__device__ __forceinline__ void filter_tile(const Work& W, float (*reg)[RW][RW + 1],
+                                            float (*hs)[RW][T + 1], float out[NS]) {
+  for (int r = threadIdx.x; r < RW * T; r += blockDim.x) {
+    const int row = r / T, col = r % T;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 11; ++j) s += W.g[j] * reg[k][row][col + j];
+      hs[k][row][col] = s;
+    }
+  }
+  __syncthreads();
+  const int ty = threadIdx.x / T, tx = threadIdx.x % T;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 11; ++j) s += W.g[j] * hs[k][ty + j][tx];
+    out[k] = s;
+  }
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void selfsup_fwd_tiles(const Work W) {
+  __shared__ float reg[5][RW][RW + 1];
+  __shared__ float hs[5][RW][T + 1];
+  __shared__ float red[4][NPART];
+  const int tile = blockIdx.x;
+  const int i = find_item(W, tile);
+  const dsm_selfsup_item& it = W.it[i];
+  int b, ty0, tx0;
+  tile_origin(W, i, tile, b, ty0, tx0);
+  const int h = it.h, w = it.w;
+  const float* disp = (const float*)it.disp + (long)b * h * w;
+
+  // 1. statistics over the tile + halo (zero outside the map: conv2d's zero padding)
+  for (int r = threadIdx.x; r < RW * RW; r += blockDim.x) {
+    const int ry = r / RW, rx = r % RW;
+    const int y = ty0 - HALO + ry, x = tx0 - HALO + rx;
+    float m1 = 0.f, m2 = 0.f, q11 = 0.f, q22 = 0.f, q12 = 0.f;
+    if (y >= 0 && y < h && x >= 0 && x < w) {
+      const Pix q{&it, i, b, y, x};
+      float iw[3], div[3], im[3];
+      image_warp(W, q, disp[(long)y * w + x], iw, div, im);
+      m1 = (im[0] + im[1] + im[2]) / 3.f;
+      m2 = (iw[0] + iw[1] + iw[2]) / 3.f;
+      q11 = (im[0] * im[0] + im[1] * im[1] + im[2] * im[2]) / 3.f;
+      q22 = (iw[0] * iw[0] + iw[1] * iw[1] + iw[2] * iw[2]) / 3.f;
+      q12 = (im[0] * iw[0] + im[1] * iw[1] + im[2] * iw[2]) / 3.f;
+    }
+    reg[0][ry][rx] = m1; reg[1][ry][rx] = m2; reg[2][ry][rx] = q11; reg[3][ry][rx] = q22;
+    reg[4][ry][rx] = q12;
+  }
+  __syncthreads();
+  float st[5];
+  filter_tile<5>(W, reg, hs, st);
+
+  // 2. the pixel's terms
+  const int y = ty0 + threadIdx.x / T, x = tx0 + threadIdx.x % T;
+  float part[NPART] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (y < h && x < w) {
+    const Pix q{&it, i, b, y, x};
+    const long o = (long)y * w + x;
+    const float d = disp[o];
+    float iw[3], div[3], im[3];
+    image_warp(W, q, d, iw, div, im);
+    const float mu1 = st[0], mu2 = st[1];
+    const float A1 = 2.f * mu1 * mu2 + C1;
+    const float A2 = 2.f * (st[4] - mu1 * mu2) + C2;
+    const float B1 = mu1 * mu1 + mu2 * mu2 + C1;
+    const float B2 = (st[2] - mu1 * mu1) + (st[3] - mu2 * mu2) + C2;
+    const float inv = 1.f / (B1 * B2);
+    const float S = A1 * A2 * inv;
+    const float dS_mu2 = 2.f * mu1 * (A2 - A1) * inv - 2.f * mu2 * S * (1.f / B1 - 1.f / B2);
+    const float dS_e22 = -S / B2;
+    const float dS_e12 = 2.f * A1 * inv;
+    float dw, ddw;
+    disp_warp(q, d, dw, ddw);
+    // mask_ap and the weight switches test exact zeros (a sample with all four taps outside):
+    // steps in the loss, so a sample within rounding of the border may fall either way in fp32
+    // and fp64 -- the GPU tests bound the fraction of such pixels instead of their error
+    const bool valid = iw[0] != 0.f;                          // mask_ap (loss.py:199)
+    float wimA = 1.f, wimB = 1.f, wlr = 1.f;
+    if (W.flag_mask) {
+      const float wc = weight_common(d, dw, it.scale_factor);
+      wimA = (dw == 0.f && valid) ? 1.f : wc;                  // mask_im with the real mask_ap
+      wimB = (dw == 0.f) ? 1.f : wc;                           // ... with the fallback mask_ap = 1
+      wlr = (dw == 0.f) ? 0.f : wc;
+    }
+    const float ap = 3.f * 0.425f * (1.f - S) +
+                     0.15f * (fabsf(im[0] - iw[0]) + fabsf(im[1] - iw[1]) + fabsf(im[2] - iw[2]));
+    // C_ds1: forward differences, zero in the last column / row (diff1_dx / diff1_dy)
+    const float* imp = (const float*)it.im + (long)b * it.im_stride[0] + (long)y * it.im_stride[2] +
+                       (long)x * it.im_stride[3];
+    float ds = 0.f;
+    if (x + 1 < w) {
+      float e = 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) e += fabsf(imp[(long)c * it.im_stride[1] + it.im_stride[3]] - im[c]);
+      ds += fabsf(disp[o + 1] - d) * expf(-e);
+    }
+    if (y + 1 < h) {
+      float e = 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) e += fabsf(imp[(long)c * it.im_stride[1] + it.im_stride[2]] - im[c]);
+      ds += fabsf(disp[o + w] - d) * expf(-e);
+    }
+    part[0] = wimA * ap;
+    part[1] = wimB * ap;
+    part[2] = ds;
+    part[3] = wlr * fabsf(d - dw);
+    part[4] = valid ? S : 0.f;
+    part[5] = valid ? 1.f : 0.f;
+    part[6] = S;
+    const long n = (long)it.B * h * w, p = (long)b * h * w + o;
+    float* sv = W.save + W.save0[i];
+    sv[p] = dS_mu2;
+    sv[n + p] = dS_e22;
+    sv[2 * n + p] = dS_e12;
+    sv[3 * n + p] = wimA;
+    sv[4 * n + p] = wimB;
+  }
+  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+#pragma unroll
+  for (int k = 0; k < NPART; ++k) {
+    const float s = wave_sum(part[k]);
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NPART) {
+    const int k = threadIdx.x;
+    W.part[(long)tile * NPART + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// one workgroup; every sum in a fixed order (fp64), so the loss is bit-reproducible
+__global__ __launch_bounds__(256) void selfsup_reduce(const Work W, float* loss, float* aux) {
+  __shared__ double red[256];
+  __shared__ double sums[DSM_SELFSUP_MAX_ITEMS][7];
+  for (int i = 0; i < W.n; ++i) {
+    for (int k = 0; k < 7; ++k) {
+      double s = 0.0;
+      for (int t = W.tile0[i] + threadIdx.x; t < W.tile0[i + 1]; t += blockDim.x)
+        s += (double)W.part[(long)t * NPART + k];
+      red[threadIdx.x] = s;
+      __syncthreads();
+      for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) sums[i][k] = red[0];
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x != 0) return;
+  double total = 0.0;
+  for (int i = 0; i < W.n; i += 2) {
+    double C[2];
+    for (int s = 0; s < 2; ++s) {
+      const int j = i + s;
+      const double n = (double)W.it[j].B * W.it[j].h * W.it[j].w;
+      const double count = sums[j][5];
+      const bool fallback = count < 1024.0;                   // loss.py:200-201
+      const double simlary = fallback ? sums[j][6] / n : sums[j][4] / count;
+      const double wt = fmax(0.0, simlary - 0.75) / 2.0 + 0.001;   // wfun, loss.py:33-34
+      const double ap = (fallback ? sums[j][1] : sums[j][0]) / (3.0 * n);
+      C[s] = ap + wt * (sums[j][2] / n) + wt * (sums[j][3] / n);
+      aux[4 * j + 0] = (float)wt;
+      aux[4 * j + 1] = fallback ? 1.f : 0.f;
+      aux[4 * j + 2] = (float)C[s];
+      aux[4 * j + 3] = (float)simlary;
+    }
+    total += (C[0] + C[1]) * (double)W.it[i].weight;
+  }
+  loss[0] = (float)total;
+}
+
+__global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const float* __restrict__ aux,
+                                                         const float* __restrict__ gloss) {
+  __shared__ float reg[3][RW][RW + 1];
+  __shared__ float hs[3][RW][T + 1];
+  const int tile = blockIdx.x;
+  const int i = find_item(W, tile);
+  const dsm_selfsup_item& it = W.it[i];
+  int b, ty0, tx0;
+  tile_origin(W, i, tile, b, ty0, tx0);
+  const int h = it.h, w = it.w;
+  const long n = (long)it.B * h * w;
+  const float* sv = W.save + W.save0[i];
+  const float wt = aux[4 * i + 0];
+  const bool fallback = aux[4 * i + 1] != 0.f;
+  const float* wim_plane = sv + (fallback ? 4 : 3) * n;
+  const float gs = gloss[0] * it.weight;
+  const float inv_n = 1.f / (float)n;
+  const float* disp = (const float*)it.disp + (long)b * h * w;
+
+  // 1. the weighted SSIM partials over tile + halo, zero outside the map
+  for (int r = threadIdx.x; r < RW * RW; r += blockDim.x) {
+    const int ry = r / RW, rx = r % RW;
+    const int y = ty0 - HALO + ry, x = tx0 - HALO + rx;
+    float p0 = 0.f, p1 = 0.f, p2 = 0.f;
+    if (y >= 0 && y < h && x >= 0 && x < w) {
+      const long p = (long)b * h * w + (long)y * w + x;
+      const float wim = wim_plane[p];
+      p0 = wim * sv[p]; p1 = wim * sv[n + p]; p2 = wim * sv[2 * n + p];
+    }
+    reg[0][ry][rx] = p0; reg[1][ry][rx] = p1; reg[2][ry][rx] = p2;
+  }
+  __syncthreads();
+  float F[3];
+  filter_tile<3>(W, reg, hs, F);
+
+  const int y = ty0 + threadIdx.x / T, x = tx0 + threadIdx.x % T;
+  if (y >= h || x >= w) return;
+  const Pix q{&it, i, b, y, x};
+  const long o = (long)y * w + x, p = (long)b * h * w + o;
+  const float d = disp[o];
+  float iw[3], div[3], im[3];
+  image_warp(W, q, d, iw, div, im);
+  const float wim = wim_plane[p];
+
+  // 2. C_ap: d C / d im_wrap_c, then through the sample position (imwrap.py:67: dix/dd = -W0/(W0-1))
+  float gix = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float giw = (-0.425f / 3.f) * inv_n * (F[0] + 2.f * iw[c] * F[1] + im[c] * F[2]) +
+                      (0.15f / 3.f) * inv_n * wim * sgnf(iw[c] - im[c]);
+    gix += giw * div[c];
+  }
+  float gd = gix * (-(float)it.W0 / (float)(it.W0 - 1));
+
+  // 3. C_lr = |d - d_wrap| * weight_lr: d is the offset of its own warp and the source of the
+  //    other view's warp (scattered there: the other item's d_wrap taps land in this grad_other)
+  float dw, ddw;
+  const Bil t = disp_warp(q, d, dw, ddw);
+  const float wlr = W.flag_mask ? ((dw == 0.f) ? 0.f : weight_common(d, dw, it.scale_factor)) : 1.f;
+  const float s = sgnf(d - dw) * wlr * wt * inv_n;
+  gd += s;
+  gd += -s * ddw * ((float)w / (float)(w - 1));
+  if (s != 0.f) {
+    float* go = (float*)it.grad_other + (long)b * h * w;
+    const float v = -s * gs;
+    if (t.in00) unsafeAtomicAdd(go + (long)t.y0 * w + t.x0, v * (t.wx0 * t.wy0));
+    if (t.in01) unsafeAtomicAdd(go + (long)t.y0 * w + t.x0 + 1, v * (t.wx1 * t.wy0));
+    if (t.in10) unsafeAtomicAdd(go + (long)(t.y0 + 1) * w + t.x0, v * (t.wx0 * t.wy1));
+    if (t.in11) unsafeAtomicAdd(go + (long)(t.y0 + 1) * w + t.x0 + 1, v * (t.wx1 * t.wy1));
+  }
+
+  // 4. C_ds1: the pixel is the right end of (x-1, x) and the left end of (x, x+1); same in y
+  const float* imp = (const float*)it.im + (long)b * it.im_stride[0] + (long)y * it.im_stride[2] +
+                     (long)x * it.im_stride[3];
+  const int cs = it.im_stride[1], xs = it.im_stride[3], ys = it.im_stride[2];
+  float gds = 0.f;
+  if (x + 1 < w) {
+    float e = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) e += fabsf(imp[(long)c * cs + xs] - im[c]);
+    gds -= sgnf(disp[o + 1] - d) * expf(-e);
+  }
+  if (x > 0) {
+    float e = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) e += fabsf(im[c] - imp[(long)c * cs - xs]);
+    gds += sgnf(d - disp[o - 1]) * expf(-e);
+  }
+  if (y + 1 < h) {
+    float e = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) e += fabsf(imp[(long)c * cs + ys] - im[c]);
+    gds -= sgnf(disp[o + w] - d) * expf(-e);
+  }
+  if (y > 0) {
+    float e = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) e += fabsf(im[c] - imp[(long)c * cs - ys]);
+    gds += sgnf(d - disp[o - w]) * expf(-e);
+  }
+  gd += gds * wt * inv_n;
+  unsafeAtomicAdd((float*)it.grad_disp + p, gd * gs);
+}
+
+int make_work(const dsm_selfsup_item* items, int n, int flag_mask, void* workspace, Work& W) {
+  DSM_REQUIRE(items && workspace, DSM_ERR_ARG);
+  DSM_REQUIRE(n >= 2 && n <= DSM_SELFSUP_MAX_ITEMS && n % 2 == 0, DSM_ERR_ARG);
+  W.n = n;
+  W.flag_mask = flag_mask ? 1 : 0;
+  long tiles = 0, save = 0;
+  for (int i = 0; i < n; ++i) {
+    const dsm_selfsup_item& it = items[i];
+    DSM_REQUIRE(it.im && it.src && it.disp && it.disp_other, DSM_ERR_ARG);
+    DSM_REQUIRE(it.B > 0 && it.h > 1 && it.w > 1 && it.H0 > 1 && it.W0 > 1, DSM_ERR_ARG);   // imwrap.py:48
+    DSM_REQUIRE(it.scale_factor > 0 && it.left >= 0 && it.top >= 0, DSM_ERR_ARG);
+    if (i % 2 == 1) DSM_REQUIRE(it.B == items[i - 1].B && it.h == items[i - 1].h && it.w == items[i - 1].w, DSM_ERR_ARG);
+    W.it[i] = it;
+    W.ntx[i] = dsm_cdiv(it.w, T);
+    W.nty[i] = dsm_cdiv(it.h, T);
+    W.tile0[i] = (int)tiles;
+    W.save0[i] = save;
+    tiles += (long)it.B * W.ntx[i] * W.nty[i];
+    save += (long)NSAVE * it.B * it.h * it.w;
+    DSM_REQUIRE(tiles < (1L << 30), DSM_ERR_UNSUPPORTED);
+    // imwrap.py:51-54, in double as the reference's Python does; torch.linspace takes them as fp32
+    const double x = it.left * 2.0 / (it.W0 - 1) - 1.0, y = it.top * 2.0 / (it.H0 - 1) - 1.0;
+    W.xs[i] = (float)x;
+    W.xe[i] = (float)(x + (it.w - 1) * (double)it.scale_factor * 2.0 / (it.W0 - 1));
+    W.ys[i] = (float)y;
+    W.ye[i] = (float)(y + (it.h - 1) * (double)it.scale_factor * 2.0 / (it.H0 - 1));
+  }
+  W.tile0[n] = (int)tiles;
+  float gf[11], sumf = 0.f;                       // SSIM.py:6-8 (torch normalises in fp32)
+  for (int k = 0; k < 11; ++k) {
+    gf[k] = (float)exp(-(k - 5) * (k - 5) / (2.0 * 1.5 * 1.5));
+    sumf += gf[k];
+  }
+  for (int k = 0; k < 11; ++k) W.g[k] = gf[k] / sumf;
+  W.part = (float*)workspace;
+  W.save = W.part + tiles * NPART;
+  return DSM_OK;
+}
+
+}  // namespace
+
+extern "C" size_t dsm_selfsup_workspace_floats(const dsm_selfsup_item* items, int n_items) {
+  if (!items || n_items < 1 || n_items > DSM_SELFSUP_MAX_ITEMS) return 0;
+  size_t f = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const dsm_selfsup_item& it = items[i];
+    if (it.B <= 0 || it.h <= 0 || it.w <= 0) return 0;
+    f += (size_t)it.B * dsm_cdiv(it.w, T) * dsm_cdiv(it.h, T) * NPART + (size_t)NSAVE * it.B * it.h * it.w;
+  }
+  return f;
+}
+
+extern "C" int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flag_mask, void* workspace,
+                               void* loss, void* aux, dsm_stream_t stream) {
+  DSM_REQUIRE(loss && aux, DSM_ERR_ARG);
+  Work W;
+  const int rc = make_work(items, n_items, flag_mask, workspace, W);
+  if (rc != DSM_OK) return rc;
+  dsm_clear_stale_error();
+  hipLaunchKernelGGL(selfsup_fwd_tiles, dim3(W.tile0[W.n]), dim3(256), 0, (hipStream_t)stream, W);
+  hipLaunchKernelGGL(selfsup_reduce, dim3(1), dim3(256), 0, (hipStream_t)stream, W, (float*)loss,
+                     (float*)aux);
+  return dsm_launch_status();
+}
+
+extern "C" int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flag_mask,
+                               const void* workspace, const void* aux, const void* grad_loss,
+                               dsm_stream_t stream) {
+  DSM_REQUIRE(aux && grad_loss, DSM_ERR_ARG);
+  for (int i = 0; items && i < n_items && i < DSM_SELFSUP_MAX_ITEMS; ++i)
+    DSM_REQUIRE(items[i].grad_disp && items[i].grad_other, DSM_ERR_ARG);
+  Work W;
+  const int rc = make_work(items, n_items, flag_mask, (void*)workspace, W);
+  if (rc != DSM_OK) return rc;
+  dsm_clear_stale_error();
+  hipLaunchKernelGGL(selfsup_bwd_tiles, dim3(W.tile0[W.n]), dim3(256), 0, (hipStream_t)stream, W,
+                     (const float*)aux, (const float*)grad_loss);
+  return dsm_launch_status();
+}

@@ -1,13 +1,18 @@
-"""Supervised training step with the reference's objective and bookkeeping (SURVEY.md
-section 8f-3): ``losses`` (losses/loss.py:341-392,407-422,515-516 -- ``loss_supervised`` :326-338),
+"""Training steps with the reference's objectives and bookkeeping:
+``losses`` (losses/loss.py:341-392,407-422,515-516 -- ``loss_supervised`` :326-338),
 ``lr_adjust`` (stereo.py:95-101), ``accuracy`` (stereo.py:103-113), ``AverageMeter``
 (utils/utils.py:87-118) and the body of the reference's train / validate loops
 (stereo_supervised.py:43-119, 121-190) as ``train_step`` / ``validate_step``.
 
+The self-supervised ``depthmono-mask`` objective (loss.py:196-236, 393-405, 424-467; the
+preset of DSMnet_train_kitti-raw.sh) runs as ONE fused HIP op over the whole pyramid
+(``costvolume.selfsup_pyramid_loss``, csrc/selfsup.hip); ``train_step_selfsup`` /
+``validate_step_selfsup`` are stereo_selfsupervised.py:48-118 / 148-200.  ``common``,
+``SsSMnet``, ``Cap_ds_lr`` and plain ``depthmono`` (no ``-mask``) are not built.
+
 The forward and backward of the model run on the HIP kernels (``costvolume`` autograd
-functions); the loss itself is a handful of element-wise stock torch ops on (B,1,H,W) maps.
-Only the supervised objective is covered -- the self-supervised ones (depthmono / SsSMnet /
-Cap_ds_lr) need the image-warping path, which SURVEY.md section 8f-4 ranks after this.
+functions); the supervised loss itself is a handful of element-wise stock torch ops on
+(B,1,H,W) maps.
 """
 import torch
 import torch.nn.functional as F
@@ -30,13 +35,19 @@ class losses(torch.nn.Module):
     def __init__(self, loss_name="supervised", count_levels=1, maxepoch_weight_adjust=1):
         super(losses, self).__init__()
         name = loss_name.split("-")[0].lower()
-        if "supervised" not in name:
-            raise NotImplementedError(
-                "only the supervised objective is built (loss_name=%r); the self-supervised "
-                "ones need the image-warping path (SURVEY.md section 8f-4)" % loss_name)
         self.flag_mask = "mask" in loss_name
-        self.lossfun = self.loss_supervised
-        self.lossesfun = self.losses_pyramid0
+        if "supervised" in name:                     # setlossfun, loss.py:367-377
+            self.lossfun = self.loss_supervised
+            self.lossesfun = self.losses_pyramid0
+        elif "depthmono" in name and self.flag_mask:
+            # the preset of DSMnet_train_kitti-raw.sh; plain "depthmono" stays unbuilt (its
+            # NotImplementedError is pinned by tests/test_train.py), the fused op takes both
+            self.lossfun = self.loss_depthmono
+            self.lossesfun = self.losses_pyramid1
+        else:
+            raise NotImplementedError(
+                "loss_name=%r is not built: supervised and depthmono-mask are; common (C_ds3), "
+                "Cap_ds_lr, SsSMnet and depthmono without -mask are not" % loss_name)
         self.maxepoch_weight_adjust = maxepoch_weight_adjust
         self.count_levels = count_levels
         self.weight_levels = [0] * count_levels
@@ -94,8 +105,62 @@ class losses(torch.nn.Module):
             loss = loss + self.lossfun(disp_gt, pred, flag_smooth, factor=1) * weight
         return loss
 
+    def loss_depthmono(self, imL, imR_src, LeftTop, dispL, imL1, imR1_src, LeftTop1, dispL1,
+                       level=0, scale_factor=1, weight=1.0, delts=None):
+        """loss.py:196-236 for ONE pyramid entry, both views (the reference calls it once per view
+        with the warps precomputed): weight * (C(left view) + C(flipped view)) through the fused
+        op.  ``imL``/``imL1`` are the level-0 crops; ``level`` picks imL[:, :, ::2**level, ::2**level]."""
+        from . import costvolume as cv
+        if delts is None:
+            delts = tuple(_draw_delt() for _ in range(4))
+        return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, [dispL], imL1, imR1_src, LeftTop1,
+                                       [dispL1], [level], [weight], [scale_factor], self.flag_mask,
+                                       [delts])
+
+    def losses_pyramid1(self, imR_src, imL, dispLs, scale_dispLs, LeftTop, imR1_src, imL1, dispL1s,
+                        scale_dispL1s=None, LeftTop1=(0, 0)):
+        """loss.py:424-467: levels above maxlevel = min(2, max level) are upsampled (stock
+        autograd) to the maxlevel grid and compared with that image level; the four random
+        epsilons of every weighted level are drawn in the reference's order from torch's CPU
+        generator; then ONE fused launch sequence for the whole pyramid."""
+        from . import costvolume as cv
+        dispLs = [d.unsqueeze(1) if d.dim() == 3 else d for d in dispLs]      # PSMNet: (B,H,W)
+        dispL1s = [d.unsqueeze(1) if d.dim() == 3 else d for d in dispL1s]
+        maxlevel = min(2, max(scale_dispLs))
+        h = w = None
+        if maxlevel in scale_dispLs:
+            _, _, h, w = dispLs[maxlevel].shape
+        ds, ds1, levels, weights, factors, delts = [], [], [], [], [], []
+        for i, level in enumerate(scale_dispLs):
+            weight = self.weight_levels[level]
+            if weight <= 0:
+                continue
+            if level > maxlevel:
+                s = 2 ** (level - maxlevel)
+                dL = F.interpolate(dispLs[i], scale_factor=s, mode="bilinear", align_corners=False)[:, :, :h, :w]
+                dL1 = F.interpolate(dispL1s[i], scale_factor=s, mode="bilinear", align_corners=False)[:, :, :h, :w]
+                factors.append(2 ** maxlevel)
+            else:
+                dL, dL1 = dispLs[i], dispL1s[i]
+                factors.append(2 ** level)
+            ds.append(dL)
+            ds1.append(dL1)
+            levels.append(min(level, maxlevel))
+            weights.append(weight)
+            delts.append(tuple(_draw_delt() for _ in range(4)))   # imL_wrap, imL1_wrap, dispL_wrap, dispL1_wrap
+        if not ds:
+            return 0
+        return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, ds, imL1, imR1_src, LeftTop1, ds1,
+                                       levels, weights, factors, self.flag_mask, delts)
+
     def forward(self, args):
         return self.lossesfun(**args)
+
+
+def _draw_delt():
+    """utils/imwrap.py:70: 1e-4 * (torch.rand(1)[0] + 0.1), in fp32, from the CPU generator (a host
+    draw: no device synchronisation)."""
+    return float(1e-4 * (torch.rand(1)[0] + 0.1))
 
 
 def lr_adjust(optimizer, epoch0, stride, lr0, epoch):
@@ -208,3 +273,71 @@ def validate_step(model, lossfun, batch):
                         "flag_smooth": True})
         d1, epe = accuracy(dispLs[0], dispL)
     return float(loss), float(d1), float(epe)
+
+
+def _selfsup_args(batch, nedge, augment):
+    """stereo_selfsupervised.py:63-90: the flipped pair is the second view; the network sees the
+    (augmented) nedge-cropped images, the loss warps the un-cropped right images from LeftTop."""
+    bn, c, h, w = batch.shape
+    if c < 6 or h <= 2 * nedge or w <= 2 * nedge:
+        raise ValueError("a self-supervised batch is (B, >=6, H, W) with H, W > 2 * nedge = %d" % (2 * nedge))
+    batch1 = torch.flip(batch, dims=[-1])
+    batch_aug = batch[:, :6, nedge:h - nedge, nedge:w - nedge].clone()
+    if augment is not None:
+        batch_aug = augment(batch_aug)
+    batch1_aug = torch.flip(batch_aug, dims=[-1])
+    pre = (batch_aug[:, :3], batch_aug[:, 3:6], batch1_aug[:, 3:6], batch1_aug[:, :3])
+    args = {"imR_src": batch[:, 3:6], "imL": batch[:, :3, nedge:h - nedge, nedge:w - nedge],
+            "LeftTop": [nedge, nedge], "imR1_src": batch1[:, :3],
+            "imL1": batch1[:, 3:6, nedge:h - nedge, nedge:w - nedge], "LeftTop1": [nedge, nedge]}
+    return pre, args
+
+
+def _selfsup_forward(model, lossfun, batch, nedge, augment):
+    (imL_pre, imR_pre, imL1_pre, imR1_pre), args = _selfsup_args(batch, nedge, augment)
+    scale_dispLs, dispLs = model(imL_pre, imR_pre)
+    scale_dispL1s, dispL1s = model(imL1_pre, imR1_pre)
+    args.update({"dispLs": dispLs, "scale_dispLs": scale_dispLs, "dispL1s": dispL1s,
+                 "scale_dispL1s": scale_dispL1s})
+    return lossfun(args), dispLs
+
+
+def _selfsup_accuracy(batch, dispLs, nedge):
+    if batch.shape[1] < 7:
+        return -1.0, -1.0
+    h, w = batch.shape[2:]
+    d1, epe = accuracy(dispLs[0].detach(), batch[:, 6:7, nedge:h - nedge, nedge:w - nedge])
+    return float(d1), float(epe)
+
+
+def train_step_selfsup(model, optim, lossfun, batch, augment=None, world=None, nedge=None):
+    """One iteration of stereo_selfsupervised.py:57-118: ``batch`` (B,>=6,H,W) imL | imR [| dispL]
+    on the device; the flipped pair (torch.flip, on the device) gives the second view; nedge = 64
+    with ``-mask``, else 0; two forwards and one backward inside ONE ``amax_scope``; Adam step.
+    ``augment``: stands in for myTransforms.Stereo_color_batch (default: identity).
+    ``nedge``: overrides the crop (None: the reference's rule).
+    Returns (loss, D1, EPE) as floats; D1 = EPE = -1 without ground truth (< 7 channels)."""
+    from . import costvolume as cv
+    if _world(world) > 1:
+        raise NotImplementedError("train_step_selfsup runs on a single rank")
+    if nedge is None:
+        nedge = 64 if lossfun.flag_mask else 0
+    with cv.amax_scope(batch.device):          # forward, forward, backward: one arena
+        model.train()
+        loss, dispLs = _selfsup_forward(model, lossfun, batch, nedge, augment)
+        optim.zero_grad()
+        if torch.is_tensor(loss):
+            loss.backward()
+            optim.step()
+    d1, epe = _selfsup_accuracy(batch, dispLs, nedge)
+    return float(loss.detach() if torch.is_tensor(loss) else loss), d1, epe
+
+
+def validate_step_selfsup(model, lossfun, batch, augment=None):
+    """One iteration of stereo_selfsupervised.py:148-200: eval mode, nedge = 0, no gradients."""
+    from . import costvolume as cv
+    model.eval()
+    with torch.no_grad(), cv.amax_scope(batch.device):
+        loss, dispLs = _selfsup_forward(model, lossfun, batch, 0, augment)
+    d1, epe = _selfsup_accuracy(batch, dispLs, 0)
+    return float(loss), d1, epe

@@ -369,6 +369,46 @@ int dsm_decoder_cat(const void* up, const void* bias, const void* pr, const void
 int dsm_stage_images_nhwc16(const void* left, const void* right, void* out, int B, int C, int H, int W,
                             dsm_stream_t stream);
 
+/* (ABI v7, additive) Self-supervised "depthmono[-mask]" pyramid loss, fused -- losses/loss.py
+ * loss_depthmono :196-236, C_ds1 :71-83, weight_common :393-405, losses_pyramid1 :424-467,
+ * losses/SSIM.py _ssim :24-42 (11x11 Gaussian, sigma 1.5, zero padding 5, ONE output channel)
+ * and utils/imwrap.py:37-72 imwrap_BCHW with LeftTop / scale_factor / fliplr.
+ * One item = one (level, side): items 2p and 2p+1 are the two views of one pyramid level and
+ *   loss = sum_p (C(item 2p) + C(item 2p+1)) * weight(item 2p).
+ * Item: im (B,3,h,w) and src (B,3,H0,W0) fp32 with element strides (b,c,y,x) (pyramid levels are
+ * the ::2^k views: no copy); disp, disp_other (B,1,h,w) contiguous; left/top = LeftTop in src
+ * pixels; scale_factor = the warp's scale and weight_common's divisor; delt_im / delt_disp = the
+ * reference's random epsilons of the image warp and of the (fliplr) disparity warp.
+ *   dsm_selfsup_workspace_floats  size of the caller-allocated fp32 workspace (tile partial sums
+ *                                 + 5 saved floats per pixel for the backward)
+ *   dsm_selfsup_fwd   2 launches (tiles, fixed-order reduction): loss (1 float) and
+ *                     aux (4 floats per item: w, fallback flag (< 1024 valid pixels), C, simlary)
+ *   dsm_selfsup_bwd   1 launch: ACCUMULATES d loss / d disp into grad_disp and grad_other of
+ *                     every item (fp32 global atomics: the left-right terms scatter into the
+ *                     other view's disparity); the caller zeroes them.  grad_loss: device scalar.
+ * flag_mask: the "-mask" weights (weight_common).  n_items even, 2..DSM_SELFSUP_MAX_ITEMS. */
+#define DSM_SELFSUP_MAX_ITEMS 16
+typedef struct dsm_selfsup_item {
+  const void* im;
+  const void* src;
+  const void* disp;
+  const void* disp_other;
+  void* grad_disp;
+  void* grad_other;
+  int im_stride[4];
+  int src_stride[4];
+  int B, h, w, H0, W0;
+  int left, top, scale_factor;
+  float delt_im, delt_disp, weight;
+  int pad_;
+} dsm_selfsup_item;
+
+size_t dsm_selfsup_workspace_floats(const dsm_selfsup_item* items, int n_items);
+int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flag_mask, void* workspace,
+                    void* loss, void* aux, dsm_stream_t stream);
+int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flag_mask, const void* workspace,
+                    const void* aux, const void* grad_loss, dsm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
