@@ -66,6 +66,15 @@ class SelfsupItem(ctypes.Structure):
                 ("pad_", c_int)]
 
 
+class ColorRecord(ctypes.Structure):
+    """struct dsm_color_record (include/dsmnet_hip.h)."""
+    _fields_ = [("order", c_int * 4), ("jitter", ctypes.c_float * 4), ("flags", c_int), ("alpha_row", c_int)]
+
+
+DSM_COLOR_JITTER, DSM_COLOR_LIGHTING, DSM_COLOR_NORMALIZE = 1, 2, 4
+DSM_COLOR_MAX_RECORDS = 64
+
+
 # name -> (restype, argtypes); must list every symbol declared in dsmnet_hip.h
 SIGNATURES = {
     "dsm_abi_version": (c_int, []),
@@ -101,6 +110,7 @@ SIGNATURES = {
     "dsm_selfsup_workspace_floats": (c_size_t, [ctypes.POINTER(SelfsupItem), c_int]),
     "dsm_selfsup_fwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
     "dsm_selfsup_bwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
+    "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),
 }
 
 _lib = None

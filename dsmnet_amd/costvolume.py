@@ -12,6 +12,7 @@ Reference code each op replaces (sunshinnnn/DSMnet):
                   models/gcnet.py:104-111
   conv3d_block    models/psmnet/submodule.py:16-19, stackhourglass.py:22-62,
                   models/util_conv.py:150-179, models/util_fun.py:41-50
+  stereo_color    myTransforms/aug_color.py:28-45, 66-101, 103-203, myTransforms/__init__.py:109-135
 """
 import ctypes
 
@@ -1282,3 +1283,46 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
             "flag_mask": bool(flag_mask)}
     loss, aux = SelfsupPyramidLossFunction.apply(spec, imL, imR_src, imL1, imR1_src, *ds)
     return (loss, aux.view(2 * n, 4)) if return_aux else loss
+
+
+# ----------------------------------------------------------------------------
+# Stereo colour augmentation (csrc/color.hip)
+# ----------------------------------------------------------------------------
+def stereo_color(x, records, alpha, groups):
+    """Rewrite the (B,C,H,W) batch ``x`` IN PLACE with the fused colour steps of
+    myTransforms.Stereo_color / Stereo_normalize (csrc/color.hip; myTransforms/aug_color.py:28-45,
+    66-101, 103-203).  ``records``: B*groups tuples ``(order, jitter, flags, alpha_row)``, record
+    b*groups + g for channels 3g..3g+2 of image b (``dsmnet_amd.transforms`` draws them);
+    ``alpha``: the (B,groups,3) device tensor of Lighting's draws (None when no record lights).
+    One launch per 64 records, on the current stream, no host synchronisation.  Returns ``x``."""
+    if not x.is_cuda:
+        _require_device("stereo_color", x)
+    if x.dtype != torch.float32:
+        raise ValueError("stereo_color: x must be float32, got %s" % x.dtype)
+    if x.dim() != 4 or x.shape[1] < 6:
+        raise ValueError("stereo_color: x must be (B, C >= 6, H, W), got %s" % (tuple(x.shape),))
+    if not x.is_contiguous():
+        raise ValueError("stereo_color: x must be a dense NCHW tensor (not a strided view)")
+    if groups not in (1, 2):
+        raise ValueError("stereo_color: groups must be 1 or 2, got %r" % (groups,))
+    B, C, H, W = x.shape
+    if len(records) != B * groups:
+        raise ValueError("stereo_color: %d records for %d images x %d groups" % (len(records), B, groups))
+    recs = (_lib.ColorRecord * len(records))()
+    lights = False
+    for r, (order, jitter, flags, row) in zip(recs, records):
+        r.order[:] = [int(o) for o in order]
+        r.jitter[:] = [float(j) for j in jitter]
+        r.flags, r.alpha_row = int(flags), int(row)
+        lights = lights or bool(r.flags & _lib.DSM_COLOR_LIGHTING)
+    if lights:
+        if alpha is None:
+            raise ValueError("stereo_color: Lighting records need the alpha tensor")
+        _require_device("stereo_color", alpha)
+        if alpha.device != x.device or not alpha.is_contiguous() or alpha.numel() < 3 * B * groups:
+            raise ValueError("stereo_color: alpha must be a dense (B, groups, 3) tensor on %s" % x.device)
+    with torch.cuda.device(x.device), _timed("stereo_color_kernel", 8.0 * B * 3 * groups * H * W):
+        rc = _lib.load().dsm_stereo_color(_p(x), _p(alpha) if lights else None, recs, len(records),
+                                          B, C, H, W, groups, _stream())
+    _lib.check(rc, "dsm_stereo_color")
+    return x

@@ -314,7 +314,8 @@ def train_step_selfsup(model, optim, lossfun, batch, augment=None, world=None, n
     """One iteration of stereo_selfsupervised.py:57-118: ``batch`` (B,>=6,H,W) imL | imR [| dispL]
     on the device; the flipped pair (torch.flip, on the device) gives the second view; nedge = 64
     with ``-mask``, else 0; two forwards and one backward inside ONE ``amax_scope``; Adam step.
-    ``augment``: stands in for myTransforms.Stereo_color_batch (default: identity).
+    ``augment``: applied to the cropped (B,6,h,w) copy in place of myTransforms.Stereo_color_batch
+    (default: identity); the reference's choice is ``transforms.Stereo_color()`` (one fused launch).
     ``nedge``: overrides the crop (None: the reference's rule).
     Returns (loss, D1, EPE) as floats; D1 = EPE = -1 without ground truth (< 7 channels)."""
     from . import costvolume as cv
@@ -334,7 +335,8 @@ def train_step_selfsup(model, optim, lossfun, batch, augment=None, world=None, n
 
 
 def validate_step_selfsup(model, lossfun, batch, augment=None):
-    """One iteration of stereo_selfsupervised.py:148-200: eval mode, nedge = 0, no gradients."""
+    """One iteration of stereo_selfsupervised.py:148-200: eval mode, nedge = 0, no gradients.
+    ``augment``: as in ``train_step_selfsup``; the reference's choice is ``transforms.Stereo_normalize()``."""
     from . import costvolume as cv
     model.eval()
     with torch.no_grad(), cv.amax_scope(batch.device):

@@ -409,6 +409,37 @@ int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flag_mask, v
 int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flag_mask, const void* workspace,
                     const void* aux, const void* grad_loss, dsm_stream_t stream);
 
+/* (ABI v7, additive) Stereo colour augmentation of a training batch, fused -- replaces
+ * myTransforms/__init__.py:109-135 Stereo_color / Stereo_normalize applied by Stereo_color_batch,
+ * i.e. myTransforms/aug_color.py ColorJitter (RandomOrder :175-203 over Brightness, Contrast,
+ * Saturation, Gamma :103-173), Lighting :66-101 and Normalize (ImageNet mean / std) :28-45.
+ * x: (B,C,H,W) dense fp32, C >= 6, rewritten IN PLACE; channels 3*groups.. are untouched.
+ * One record per (image, group), record b*groups + g for channels 3g..3g+2 of image b, drawn on the
+ * host.  Per pixel and group, in this order:
+ *   DSM_COLOR_JITTER     the four steps in order[0..3] (0 Brightness x*j[0], 1 Contrast x+j[1],
+ *                        2 Saturation x+gray*j[2], 3 Gamma max(x,0)^j[3]), then clamp(0,1);
+ *   DSM_COLOR_LIGHTING   x += sum_c eigvec[r][c]*alpha[c]*eigval[c] (ImageNet PCA), clamp(0,1);
+ *                        alpha = the 3 floats at alpha + 3*alpha_row (device memory, fp32);
+ *   DSM_COLOR_NORMALIZE  (x - mean) / std.
+ * j[] holds the scalars as the reference applies them (Brightness / Gamma: 1 + u; Contrast /
+ * Saturation: u).  Gamma clamps its base at 0 where the reference yields NaN.
+ * groups 1 or 2; n_recs == B*groups; order a permutation of 0..3; alpha_row in [0, B*groups) when
+ * LIGHTING is set (alpha may be NULL otherwise).  Records travel in kernel arguments, up to
+ * DSM_COLOR_MAX_RECORDS per launch (larger batches: one launch per chunk); no host synchronisation. */
+#define DSM_COLOR_JITTER     1
+#define DSM_COLOR_LIGHTING   2
+#define DSM_COLOR_NORMALIZE  4
+#define DSM_COLOR_MAX_RECORDS 64
+typedef struct dsm_color_record {
+  int order[4];
+  float jitter[4];
+  int flags;
+  int alpha_row;
+} dsm_color_record;
+
+int dsm_stereo_color(void* x, const void* alpha, const dsm_color_record* recs, int n_recs, int B, int C,
+                     int H, int W, int groups, dsm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
