@@ -111,6 +111,7 @@ SIGNATURES = {
     "dsm_selfsup_fwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
     "dsm_selfsup_bwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
     "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),
+    "dsm_concat_conv_fwd": (c_int, [c_void_p] * 5 + [c_size_t] + [c_void_p] * 2 + [c_int] * 9 + [c_void_p]),
 }
 
 _lib = None

@@ -52,6 +52,7 @@ class _Folded(object):
     def __init__(self):
         self.key = None
         self.packed = self.scale = self.shift = None
+        self.separable = None          # the same weight in costvolume.pack_concat_conv_weight order (made on demand)
 
     def get(self, conv, bn):
         transposed = isinstance(conv, nn.ConvTranspose3d)
@@ -62,6 +63,7 @@ class _Folded(object):
         if key != self.key:
             with torch.no_grad():
                 self.packed = cv.pack_conv3d_weight(conv.weight, transposed)
+                self.separable = None
                 cout = conv.out_channels
                 if bn is not None:
                     inv = torch.rsqrt(bn.running_var + bn.eps)
@@ -160,6 +162,13 @@ def run_block(folded, conv, bn, x, residual=None, relu=RELU_NONE):
             y = torch.relu(y)
         return y
     packed, scale, shift = folded.get(conv, bn)
+    transposed = isinstance(conv, nn.ConvTranspose3d)
+    if residual is None and cv.concat_conv_ok(x, conv.out_channels, conv.stride[0], transposed):
+        # first layer on a virtual cost volume: 2-D maps + broadcast (option "separable_volume")
+        if folded.separable is None:
+            with torch.no_grad():
+                folded.separable = cv.pack_concat_conv_weight(conv.weight)
+        return cv.concat_conv_block(x, folded.separable, scale, shift, relu != RELU_NONE)
     return cv.conv3d_block(x, packed, conv.out_channels, scale, shift, residual,
                            stride=conv.stride[0], transposed=isinstance(conv, nn.ConvTranspose3d),
                            relu=relu)

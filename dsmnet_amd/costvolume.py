@@ -411,7 +411,15 @@ def _env_precision():
     return v or "f16x2"
 
 
-_OPTIONS = {"fuse_volume": True, "fuse_blocks": True, "conv_precision": _env_precision(), "conv_flags": 0}
+def _env_flag(name, default):
+    v = _os.environ.get(name, "")
+    if v not in ("", "0", "1"):
+        raise ValueError("%s must be 0 or 1, got %r" % (name, v))
+    return default if v == "" else v == "1"
+
+
+_OPTIONS = {"fuse_volume": True, "fuse_blocks": True, "conv_precision": _env_precision(), "conv_flags": 0,
+            "separable_volume": _env_flag("DSM_SEPARABLE_VOLUME", True), "separable_flags": 0}
 
 
 def set_option(name, value):
@@ -425,6 +433,9 @@ def set_option(name, value):
     ``conv_fp32`` -- older spelling: True = "fp32", False = "bf16x3";
     ``fuse_volume`` -- PSMNet's / GCNet's eval forward never materialises the cost volume: the first
     3-D convolution stages it from the feature maps;
+    ``separable_volume`` -- the first 3-D convolution of a never-materialised volume runs as 2-D maps
+    plus a broadcast (``concat_conv_block``) instead of the z-sliding kernel; starts from
+    DSM_SEPARABLE_VOLUME=0|1 (default on); ``separable_flags``: raw tuning bits of dsm_concat_conv_fwd;
     ``fuse_blocks`` -- the towers' stride-1 64-channel BasicBlocks run as one launch each (fp16 modes);
     ``conv_flags`` -- raw dsm_conv3d_args.flags bits (tile height, grid size)."""
     if name == "conv_fp32":
@@ -439,7 +450,7 @@ def set_option(name, value):
             raise ValueError("conv_precision must be one of %s" % (_PRECISIONS,))
         _OPTIONS[name] = value
     else:
-        _OPTIONS[name] = int(value) if name == "conv_flags" else bool(value)
+        _OPTIONS[name] = int(value) if name in ("conv_flags", "separable_flags") else bool(value)
     return old
 
 
@@ -610,6 +621,65 @@ def virtual_volume_ok(C):
     """The z-sliding kernel can stage a virtual volume of 2C channels (C % 32 == 0) in every
     precision except "fp32" (which has no split kernels)."""
     return C % 32 == 0 and _OPTIONS["conv_precision"] != "fp32"
+
+
+# ----------------------------------------------------------------------------
+# first convolution of a virtual cost volume from 2-D maps (csrc/sepvol.hip, DESIGN.md 3.2f)
+# ----------------------------------------------------------------------------
+def pack_concat_conv_weight(weight):
+    """Conv3d weight (32, 2C, 3, 3, 3) of the layer that reads a concatenation volume ->
+    [side][dz][dx][dy][C/2][2][32] (flat): the operand order of ``dsm_concat_conv_fwd``'s column
+    convolutions -- input channel ``side*C + h*C/2 + cc`` sits at [..][cc][h][..].  A pure
+    permutation (no sums), any device."""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or weight.shape[1] % 4:
+        raise ValueError("pack_concat_conv_weight: expected (Cout, 2C, 3, 3, 3) with C even, got %s"
+                         % (tuple(weight.shape),))
+    cout, c2 = weight.shape[:2]
+    w = weight.detach().reshape(cout, 2, 2, c2 // 4, 3, 3, 3)         # o, side, h, cc, dz, dy, dx
+    return w.permute(1, 4, 6, 5, 3, 2, 0).contiguous().reshape(-1)
+
+
+def concat_conv_ok(x, cout, stride=1, transposed=False):
+    """Does ``concat_conv_block`` cover this layer (else: ``conv3d_block`` on the z-sliding kernel)?"""
+    return (_OPTIONS["separable_volume"] and isinstance(x, VirtualVolume) and cout == 32 and stride == 1 and
+            not transposed and x.shape[1] // 2 in (32, 64) and x.shape[0] * x.shape[3] <= 65535)
+
+
+def concat_conv_workspace_floats(B, H, W):
+    return 32 * H * (18 * B * W + 4 * B * (2 * W + 2))
+
+
+def concat_conv_block(x, sep_weight, scale=None, shift=None, relu=False):
+    """y = relu?(conv3d(volume) * scale + shift) for a ``VirtualVolume`` ``x`` and a Conv3d(2C -> 32, k3,
+    s1, p1) whose weight was packed by ``pack_concat_conv_weight``: the volume's planes are shifted
+    copies of two 2-D maps, so the convolution is 2-D column convolutions of the towers' output
+    (fp32-input MFMA), their sums F and G, and one pass that writes F[y, x] + G[y, x - d] (the general
+    18-term form at the borders) -- three launches, no volume, no 3-D arithmetic.  Independent of
+    ``conv_precision``; the result carries its exact absolute maximum in the fp16 modes.
+    Returns (B, 32, D, H, W) channels_last_3d.  Inference only."""
+    if not isinstance(x, VirtualVolume):
+        raise TypeError("concat_conv_block takes a VirtualVolume")
+    both = x.features
+    _require_device("concat_conv_block", both, sep_weight, scale, shift)
+    B, c2, D, H, W = x.shape
+    C = c2 // 2
+    if sep_weight.numel() != 27 * 32 * c2:
+        raise ValueError("concat_conv_block: packed weight has %d floats, expected %d"
+                         % (sep_weight.numel(), 27 * 32 * c2))
+    y = torch.empty((B, 32, D, H, W), device=both.device, dtype=torch.float32, memory_format=_CL3D)
+    nws = concat_conv_workspace_floats(B, H, W)
+    ws = torch.empty(nws, device=both.device, dtype=torch.float32)
+    ya = _ARENA.slot(both.device) if needs_amax() else None
+    # HBM-side bytes: the features in, the output out (the K / F / G workspace stays in the caches)
+    work = 4.0 * (both.numel() + y.numel())
+    with torch.cuda.device(both.device), _timed("sepvol_fwd_kernel", work):
+        rc = _lib.load().dsm_concat_conv_fwd(_p(both), _p(sep_weight), _p(scale), _p(shift), _p(ws), nws,
+                                             _p(y), _p(ya), B, C, 32, D, H, W, int(x.mask_left),
+                                             int(bool(relu)), _OPTIONS["separable_flags"], _stream())
+    _lib.check(rc, "dsm_concat_conv_fwd")
+    if ya is not None:
+        y._dsm_amax = ya
+    return y
 
 
 # ----------------------------------------------------------------------------

@@ -440,6 +440,29 @@ typedef struct dsm_color_record {
 int dsm_stereo_color(void* x, const void* alpha, const dsm_color_record* recs, int n_recs, int B, int C,
                      int H, int W, int groups, dsm_stream_t stream);
 
+/* (ABI v7, additive) First convolution of a concatenation cost volume, from 2-D maps (csrc/sepvol.hip,
+ * DESIGN.md 3.2f): y = relu?(conv3d(volume, W; k3 s1 p1) * scale + shift) for the volume of
+ * dsm_concat_volume_fwd, which is never formed -- plane d is [left | right shifted by d], so the
+ * convolution is F[y, x] + G[y, x - d] of two 2-D images away from the borders, and a sum of 18
+ * guarded column-convolution images (KL / KR [dz][dx]) everywhere.  Three launches: the K images
+ * (exact fp32-input MFMA), the F / G sums, the broadcast that writes y.  Inference only.
+ *   both       (2B, H, W, C) NHWC fp32: the B left maps, then the B right maps; C = 32 or 64
+ *              (other multiples of 32: DSM_ERR_UNSUPPORTED -- use dsm_conv3d_fwd with vol_virtual)
+ *   w_packed   the (32, 2C, 3,3,3) weight as [side][dz][dx][dy][C/2][2][32 outputs] fp32:
+ *              input channel side*C + h*C/2 + cc at [..][cc][h][..]
+ *   scale, shift  32 floats each (folded BN), or NULL (1 / 0)
+ *   workspace  32*H*(18*B*W + 4*B*(2*W + 2)) floats or more (workspace_floats says how many)
+ *   y          (B, D, H, W, 32) NDHWC fp32, fully overwritten
+ *   y_amax     NULL, or the device scalar raised to max |y| (atomic max, as dsm_conv3d_args.y_amax)
+ *   Cout       must be 32; D, H, W >= 1 (every size works: D < 3 and W < 5 take the general form)
+ *   mask_left  nonzero: the left half is zeroed for x < d too (PSMNet); zero: GCNet
+ *   flags      0, or tuning: planes per workgroup (default 12) | columns per workgroup << 8 (default 107) |
+ *              plain instead of nontemporal stores << 20 */
+int dsm_concat_conv_fwd(const void* both, const void* w_packed, const void* scale, const void* shift,
+                        void* workspace, size_t workspace_floats, void* y, float* y_amax,
+                        int B, int C, int Cout, int D, int H, int W,
+                        int mask_left, int relu, int flags, dsm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
