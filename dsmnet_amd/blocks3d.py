@@ -15,8 +15,9 @@ from . import costvolume as cv
 
 RELU_NONE, RELU_AFTER_ADD, RELU_BEFORE_ADD = 0, 1, 2
 _FUSED_TRAIN_BN = __import__("os").environ.get("DSM_TRAIN_BN", "fused") != "stock"
-# test hook: called with (block output, relu mode) of every fused train-mode block that ends in a
-# ReLU (the sign pattern of the ReLU's input is `out > 0` for mode 1)
+# test hook: called with (block output, relu mode, residual) of every fused train-mode block that ends
+# in a ReLU (the sign pattern of the ReLU's input is `out > 0` for mode 1, `out > residual`, cropped to
+# out, for mode 2)
 _TRAIN_RELU_HOOK = [None]
 
 
@@ -117,7 +118,7 @@ def _run_block_batch_stats(folded, conv, bn, x, residual, relu):
             bn.num_batches_tracked += 1
         _bump_running_stats(bn)
         if _TRAIN_RELU_HOOK[0] is not None and relu != RELU_NONE:
-            _TRAIN_RELU_HOOK[0](out, relu)
+            _TRAIN_RELU_HOOK[0](out, relu, residual)
         return out
     y = torch.nn.functional.batch_norm(y, bn.running_mean, bn.running_var, bn.weight, bn.bias,
                                        True, momentum, bn.eps)

@@ -493,7 +493,7 @@ __global__ void wgrad_permute_kernel(const float* __restrict__ ws, float* __rest
 }
 
 template <int PM, int S, int TY, int KZ, int DIL>
-int launch_wgrad_split(WgradParams p, float* dw, hipStream_t s) {
+int launch_wgrad_split(WgradParams p, float* dw, int force_bx, hipStream_t s) {
   using G = WgradGeo<S, TY, KZ, DIL, WPrec<PM>::NP>;
   static_assert(G::LDS <= 160 * 1024, "LDS");
   static_assert(KZ == 3 || (TY * 2) % 4 == 0, "KZ = 1 splits the k-blocks over the four waves");
@@ -504,6 +504,7 @@ int launch_wgrad_split(WgradParams p, float* dw, hipStream_t s) {
   DSM_REQUIRE(nt < (1L << 30), DSM_ERR_UNSUPPORTED);
   p.ntiles = (int)nt;
   int bx = 256 / p.npair; if (bx < 1) bx = 1;
+  if (force_bx > 0) bx = force_bx;                 // flags bits 16..31: the persistent grid size, forced
   if (bx > p.ntiles) bx = p.ntiles;
   static thread_local bool configured = false;
   if (!configured) {
@@ -520,7 +521,7 @@ int launch_wgrad_split(WgradParams p, float* dw, hipStream_t s) {
 }
 
 template <int S, int TY, int KZ, int DIL>
-int launch_wgrad(WgradParams p, float* dw, hipStream_t s) {
+int launch_wgrad(WgradParams p, float* dw, int force_bx, hipStream_t s) {
   constexpr int IY = (TY - 1) * S + 2 * DIL + 1, IX = 31 * S + 2 * DIL + 1;
   constexpr int NTAP = 9 * KZ;
   constexpr size_t lds = (size_t)(KZ * IY * IX * 8 + TY * 32 * 8) * 16;
@@ -532,6 +533,7 @@ int launch_wgrad(WgradParams p, float* dw, hipStream_t s) {
   DSM_REQUIRE(nt < (1L << 30), DSM_ERR_UNSUPPORTED);
   p.ntiles = (int)nt;
   int bx = 256 / p.npair; if (bx < 1) bx = 1;
+  if (force_bx > 0) bx = force_bx;                 // flags bits 16..31: the persistent grid size, forced
   if (bx > p.ntiles) bx = p.ntiles;
   static thread_local bool configured = false;
   if (!configured) {
@@ -817,6 +819,8 @@ __global__ __launch_bounds__(256) void deconv_cout1_bwd_weight_kernel(
 
 // x: (B,Dx,Hx,Wx,Cx) NDHWC; g: (B,Dg,Hg,Wg,Cg); stride: X positions per G position (1 or 2);
 // ws: workspace of (Cx/32)*(Cg/32)*27*32*32 floats (zeroed here); dw: (Cg, Cx, 27), overwritten.
+// flags: DSM_CONV_FP32_MFMA picks the fp32-input kernel; bits 16..31 (DSM_CONV_BLOCKS_SHIFT), when not
+// zero, force the persistent grid's x size (workgroups per channel pair; clamped to [1, units]).
 extern "C" int dsm_conv3d_wgrad(const void* x, const void* g, void* ws, void* dw, int B, int Cx,
                                 int Cg, int Dx, int Hx, int Wx, int Dg, int Hg, int Wg, int stride,
                                 int flags, int precision, const float* x_amax, const float* g_amax,
@@ -836,21 +840,23 @@ extern "C" int dsm_conv3d_wgrad(const void* x, const void* g, void* ws, void* dw
   p.B = B; p.Cx = Cx; p.Cg = Cg; p.Dx = Dx; p.Hx = Hx; p.Wx = Wx; p.Dg = Dg; p.Hg = Hg; p.Wg = Wg;
   p.npair = (Cx / 32) * (Cg / 32);
   p.x_amax = x_amax; p.g_amax = g_amax;
+  const int fbx = (flags >> DSM_CONV_BLOCKS_SHIFT) & 0xffff;
   if (!(flags & DSM_CONV_FP32_MFMA)) {             // fp32 operands on the 16-bit matrix pipe
 #define DSM_WG3(PM_) \
-    if (stride == 1) return launch_wgrad_split<PM_, 1, 4, 3, 1>(p, (float*)dw, s); \
-    return launch_wgrad_split<PM_, 2, 1, 3, 1>(p, (float*)dw, s)
+    if (stride == 1) return launch_wgrad_split<PM_, 1, 4, 3, 1>(p, (float*)dw, fbx, s); \
+    return launch_wgrad_split<PM_, 2, 1, 3, 1>(p, (float*)dw, fbx, s)
     if (precision == DSM_PREC_F16X2) { DSM_WG3(2); }
     if (precision == DSM_PREC_F16) { DSM_WG3(1); }
     DSM_WG3(3);
 #undef DSM_WG3
   }
-  if (stride == 1) return launch_wgrad<1, 4, 3, 1>(p, (float*)dw, s);
-  return launch_wgrad<2, 2, 3, 1>(p, (float*)dw, s);
+  if (stride == 1) return launch_wgrad<1, 4, 3, 1>(p, (float*)dw, fbx, s);
+  return launch_wgrad<2, 2, 3, 1>(p, (float*)dw, fbx, s);
 }
 
 // The same for the 2-D towers' 3x3 layers (padding = dilation): x: (B,Hx,Wx,Cx) NHWC,
 // g: (B,Hg,Wg,Cg); ws: (Cx/32)*(Cg/32)*9*32*32 floats; dw: (Cg, Cx, 3, 3), overwritten.
+// flags: as for dsm_conv3d_wgrad (bits 16..31 force the grid's x size).
 extern "C" int dsm_conv2d_wgrad(const void* x, const void* g, void* ws, void* dw, int B, int Cx,
                                 int Cg, int Hx, int Wx, int Hg, int Wg, int stride, int dilation,
                                 int flags, int precision, const float* x_amax, const float* g_amax,
@@ -870,19 +876,20 @@ extern "C" int dsm_conv2d_wgrad(const void* x, const void* g, void* ws, void* dw
   p.B = B; p.Cx = Cx; p.Cg = Cg; p.Dx = 1; p.Hx = Hx; p.Wx = Wx; p.Dg = 1; p.Hg = Hg; p.Wg = Wg;
   p.npair = (Cx / 32) * (Cg / 32);
   p.x_amax = x_amax; p.g_amax = g_amax;
+  const int fbx = (flags >> DSM_CONV_BLOCKS_SHIFT) & 0xffff;
   if (!(flags & DSM_CONV_FP32_MFMA)) {
 #define DSM_WG2(PM_) \
-    if (stride == 2) return launch_wgrad_split<PM_, 2, 4, 1, 1>(p, (float*)dw, s); \
-    if (dilation == 2) return launch_wgrad_split<PM_, 1, 8, 1, 2>(p, (float*)dw, s); \
-    return launch_wgrad_split<PM_, 1, 8, 1, 1>(p, (float*)dw, s)
+    if (stride == 2) return launch_wgrad_split<PM_, 2, 4, 1, 1>(p, (float*)dw, fbx, s); \
+    if (dilation == 2) return launch_wgrad_split<PM_, 1, 8, 1, 2>(p, (float*)dw, fbx, s); \
+    return launch_wgrad_split<PM_, 1, 8, 1, 1>(p, (float*)dw, fbx, s)
     if (precision == DSM_PREC_F16X2) { DSM_WG2(2); }
     if (precision == DSM_PREC_F16) { DSM_WG2(1); }
     DSM_WG2(3);
 #undef DSM_WG2
   }
-  if (stride == 2) return launch_wgrad<2, 4, 1, 1>(p, (float*)dw, s);
-  if (dilation == 2) return launch_wgrad<1, 8, 1, 2>(p, (float*)dw, s);
-  return launch_wgrad<1, 8, 1, 1>(p, (float*)dw, s);
+  if (stride == 2) return launch_wgrad<2, 4, 1, 1>(p, (float*)dw, fbx, s);
+  if (dilation == 2) return launch_wgrad<1, 8, 1, 2>(p, (float*)dw, fbx, s);
+  return launch_wgrad<1, 8, 1, 1>(p, (float*)dw, fbx, s);
 }
 
 // Cout = 1 convolution (stride 1): g: (B,D,H,W); x: (B,D,H,W,C); w_packed: [27][C] (as packed
@@ -893,12 +900,16 @@ extern "C" int dsm_conv3d_cout1_bwd(const void* x, const void* g, const void* w_
   DSM_REQUIRE(g && (dx || dw_tapmajor), DSM_ERR_ARG);
   DSM_REQUIRE(B > 0 && C > 0 && C % 4 == 0 && D > 0 && H > 0 && W > 0, DSM_ERR_ARG);
   DSM_REQUIRE((long)B * D * H <= 0x7fffffffL, DSM_ERR_UNSUPPORTED);
+  DSM_REQUIRE(!dx || w_packed, DSM_ERR_ARG);
+  DSM_REQUIRE(!dw_tapmajor || x, DSM_ERR_ARG);
+  // both bwd-data kernels read w_packed and write dx as 16-byte quads (x is read as quads by the tile
+  // kernels only: an unaligned x takes the scalar bwd-weight kernel)
+  DSM_REQUIRE(!dx || (dsm_aligned16(w_packed) && dsm_aligned16(dx)), DSM_ERR_ALIGN);
   hipStream_t s = (hipStream_t)stream;
   dsm_clear_stale_error();
   if (dx) {
-    DSM_REQUIRE(w_packed, DSM_ERR_ARG);
     const long n = (long)B * D * H * W * (C / 4);
-    if (C == 32 && dsm_aligned16(w_packed) && dsm_aligned16(dx))
+    if (C == 32)
       hipLaunchKernelGGL(cout1_bwd_data32_kernel, dim3(dsm_cdiv(n / 8, 256)), dim3(256), 0, s,
                          (const float*)g, (const float*)w_packed, (float*)dx, B, D, H, W);
     else
@@ -906,7 +917,6 @@ extern "C" int dsm_conv3d_cout1_bwd(const void* x, const void* g, const void* w_
                          (const float*)g, (const float*)w_packed, (float*)dx, B, C, D, H, W);
   }
   if (dw_tapmajor) {
-    DSM_REQUIRE(x, DSM_ERR_ARG);
     if (hipMemsetAsync(dw_tapmajor, 0, (size_t)27 * C * sizeof(float), s) != hipSuccess)
       return DSM_ERR_LAUNCH;
     const long ntile32 = (long)B * D * H * dsm_cdiv(W, 32);
@@ -935,10 +945,12 @@ extern "C" int dsm_deconv3d_cout1_bwd(const void* x, const void* g, const void* 
   DSM_REQUIRE(B > 0 && C > 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0, DSM_ERR_ARG);
   DSM_REQUIRE(C % 4 == 0 && C <= 256, DSM_ERR_UNSUPPORTED);
   DSM_REQUIRE(Do <= 2 * Di && Ho <= 2 * Hi && Wo <= 2 * Wi, DSM_ERR_ARG);
+  DSM_REQUIRE(!dx || w, DSM_ERR_ARG);
+  DSM_REQUIRE(!dw || x, DSM_ERR_ARG);
+  DSM_REQUIRE(!dx || dsm_aligned16(dx), DSM_ERR_ALIGN);   // dx leaves as 16-byte quads
   hipStream_t s = (hipStream_t)stream;
   dsm_clear_stale_error();
   if (dx) {
-    DSM_REQUIRE(w, DSM_ERR_ARG);
     const long n = (long)B * Di * Hi * Wi * (C / 4);
     DSM_REQUIRE(n / 256 < 0x7fffffffL, DSM_ERR_UNSUPPORTED);
     hipLaunchKernelGGL(deconv_cout1_bwd_data_kernel, dim3(dsm_cdiv(n, 256)), dim3(256),
@@ -946,7 +958,6 @@ extern "C" int dsm_deconv3d_cout1_bwd(const void* x, const void* g, const void* 
                        (float*)dx, B, C, Di, Hi, Wi, Do, Ho, Wo);
   }
   if (dw) {
-    DSM_REQUIRE(x, DSM_ERR_ARG);
     if (hipMemsetAsync(dw, 0, (size_t)27 * C * sizeof(float), s) != hipSuccess) return DSM_ERR_LAUNCH;
     const long nvox = (long)B * Di * Hi * Wi;
     const int nvl = 256 / C;

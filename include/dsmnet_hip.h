@@ -252,6 +252,9 @@ int dsm_conv3d_plan(const dsm_conv3d_args* args, char* buf, int len);
  * transposed LDS read.  precision (ABI v6, DSM_PREC_*): bf16x3 (DSM_PREC_F32), or the fp16 forms
  * f16x2 / f16, which scale X and G by powers of two taken from the device scalars x_amax / g_amax
  * (max |X|, max |G|; required then -- dsm_absmax or a producer's y_amax).
+ * flags bits 16..31 (DSM_CONV_BLOCKS_SHIFT), when not zero, force the number of persistent workgroups
+ * per 32 x 32 channel pair (clamped to [1, work units]; tests walk long ranges with it); 0 keeps the
+ * launcher's own choice, min(256 / pairs, units).
  * ------------------------------------------------------------------------- */
 int dsm_conv3d_wgrad(const void* x, const void* g, void* ws, void* dw, int B, int Cx, int Cg,
                      int Dx, int Hx, int Wx, int Dg, int Hg, int Wg, int stride, int flags,
@@ -260,13 +263,15 @@ int dsm_conv3d_wgrad(const void* x, const void* g, void* ws, void* dw, int B, in
 /* (ABI v5) The same for the 2-D towers' 3x3 layers -- autograd through convbn / BasicBlock
  * (models/psmnet/submodule.py:10-13,24-46) when the feature extraction trains.  padding = dilation;
  * (stride, dilation) in {(1,1), (1,2), (2,1)}.  x: (B,Hx,Wx,Cx) NHWC, g: (B,Hg,Wg,Cg) NHWC;
- * ws: (Cx/32)*(Cg/32)*9*32*32 floats (zeroed here); dw: (Cg, Cx, 3, 3) torch layout, overwritten. */
+ * ws: (Cx/32)*(Cg/32)*9*32*32 floats (zeroed here); dw: (Cg, Cx, 3, 3) torch layout, overwritten.
+ * flags: as for dsm_conv3d_wgrad, the forced grid size in bits 16..31 included. */
 int dsm_conv2d_wgrad(const void* x, const void* g, void* ws, void* dw, int B, int Cx, int Cg,
                      int Hx, int Wx, int Hg, int Wg, int stride, int dilation, int flags,
                      int precision, const float* x_amax, const float* g_amax, dsm_stream_t stream);
 
 /* Cout = 1, stride 1 (classifier heads): g (B,D,H,W); x (B,D,H,W,C); w_packed [27][C];
- * dx (B,D,H,W,C) or NULL; dw_tapmajor [27][C] or NULL (the caller transposes to (1,C,27)). */
+ * dx (B,D,H,W,C) or NULL; dw_tapmajor [27][C] or NULL (the caller transposes to (1,C,27)).
+ * w_packed and dx must be 16-byte aligned when dx is asked for (DSM_ERR_ALIGN, nothing launched). */
 int dsm_conv3d_cout1_bwd(const void* x, const void* g, const void* w_packed, void* dx,
                          void* dw_tapmajor, int B, int C, int D, int H, int W,
                          dsm_stream_t stream);
@@ -274,7 +279,7 @@ int dsm_conv3d_cout1_bwd(const void* x, const void* g, const void* w_packed, voi
 /* ConvTranspose3d(C -> 1, k3, s2, p1, op1) backward -- GCNet's head l37 (models/gcnet.py:63,98;
  * autograd through nn.ConvTranspose3d in the reference).  g (B,Do,Ho,Wo); x (B,Di,Hi,Wi,C)
  * NDHWC; w: torch layout (C,1,3,3,3); dx (B,Di,Hi,Wi,C) or NULL; dw (C,1,3,3,3) or NULL,
- * overwritten.  C % 4 == 0, C <= 256. */
+ * overwritten.  C % 4 == 0, C <= 256; dx 16-byte aligned (DSM_ERR_ALIGN, nothing launched). */
 int dsm_deconv3d_cout1_bwd(const void* x, const void* g, const void* w, void* dx, void* dw,
                            int B, int C, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
                            dsm_stream_t stream);

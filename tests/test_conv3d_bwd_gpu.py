@@ -67,7 +67,7 @@ class _SignLog(object):
         return relu
 
 
-def _trunk_step_errors(seed, hw=(16, 40), d4=8):
+def _trunk_step_errors(seed, hw=(16, 40), d4=8, batch=1):
     """One train-mode trunk + heads step on a seeded input: relative max-abs error of every
     checked gradient against the oracle's CPU autograd, and the number of ReLU inputs whose SIGN
     differs between the two implementations.
@@ -90,7 +90,7 @@ def _trunk_step_errors(seed, hw=(16, 40), d4=8):
     from dsmnet_amd.models import model_create_by_name
     sd = randomise_bn(OM.init_state("psmnet", 0), 41)
     OM.apply_head_scale("psmnet", sd, 0.05)
-    fl, fr = seeded(seed, 1, 32, *hw), seeded(seed + 1, 1, 32, *hw)
+    fl, fr = seeded(seed, batch, 32, *hw), seeded(seed + 1, batch, 32, *hw)
     size = (4 * d4, 4 * hw[0], 4 * hw[1])
     keys = ["dres0.0.0.weight", "dres0.0.1.weight", "dres1.2.0.weight", "dres2.conv1.0.0.weight",
             "dres2.conv5.0.weight", "dres3.conv6.0.weight", "dres4.conv2.1.bias",
@@ -103,7 +103,7 @@ def _trunk_step_errors(seed, hw=(16, 40), d4=8):
     glog = _SignLog()
     # the product's train-mode blocks are fused (BatchNorm + add + ReLU in one kernel): the sign
     # pattern of the ReLU's input is read off the block's output (out > 0 <=> input > 0)
-    blocks3d._TRAIN_RELU_HOOK[0] = lambda out, mode: glog.masks.append((out.detach() > 0).cpu())
+    blocks3d._TRAIN_RELU_HOOK[0] = lambda out, mode, residual: glog.masks.append((out.detach() > 0).cpu())
     orig_t = torch.relu
     torch.relu = glog.wrap(orig_t)                 # (DSM_TRAIN_BN=stock: blocks3d calls torch.relu)
     try:
@@ -181,6 +181,107 @@ def test_psmnet_trunk_training_step_at_config5_shape(hip_lib):
     (135 -> 68 -> 34 -> 68 -> 136 vs 135; stackhourglass.py:10-20) in forward AND backward.
     Gradients against the oracle's CPU autograd with the product's ReLU masks forced: GRAD_TOL."""
     errs, flips, units = _trunk_step_errors(91, hw=(135, 240), d4=48)
+    _check_gradients(errs, flips, units)
+
+
+def test_psmnet_trunk_training_step_batch_2_odd_sizes(hip_lib):
+    """Two pairs, features (2,32,15,38), D/4 = 7: every ``myadd_3d`` crop in forward and backward
+    (7 -> 4 -> 2 -> 4 -> 8 vs 7; 15 -> 8 -> 4 -> 8 -> 16 vs 15; 38 -> 19 -> 10 -> 20 vs 19) with a batch
+    boundary inside every kernel's work list.  Same bound and flip budget as at batch 1."""
+    errs, flips, units = _trunk_step_errors(61, hw=(15, 38), d4=7, batch=2)
+    _check_gradients(errs, flips, units)
+
+
+def _gcnet_step_errors(seed, batch=2, hw=(21, 42), d2=12):
+    """``_trunk_step_errors`` for GCNet: 3-D trunk (models/gcnet.py:65-101) + the transposed 32 -> 1 head
+    ``l37`` + soft-argmin of the negated cost, in train mode, on a seeded 1/2-resolution feature pair.
+
+    GCNet's blocks end in their own ReLU and add the skip AFTER it (``relu == RELU_BEFORE_ADD``), so the
+    sign of the ReLU's input is not ``out > 0`` there: it is ``out > residual`` on the cropped corner the
+    output covers.  Outside that corner the transposed convolution's values are dropped by the crop and
+    carry no gradient: the oracle keeps its own sign there.  A positive value that the addition absorbs
+    (relu(y) + r == r in fp32) reads as a flip and is counted by the flip budget.
+    Sizes: (12,21,42) -> (6,11,21) -> (3,6,11) -> (2,3,6) -> (1,2,3) and back up through
+    (2,4,6) / (4,6,12) / (6,12,22) / (12,22,42): every skip addition crops."""
+    import torch.nn.functional as TF
+    from dsmnet_amd import blocks3d
+    from dsmnet_amd import costvolume as cv
+    from dsmnet_amd.models import model_create_by_name
+    sd = randomise_bn(OM.init_state("gcnet", 0), 43)
+    OM.apply_head_scale("gcnet", sd, 0.05)
+    fl, fr = seeded(seed, batch, 32, *hw), seeded(seed + 1, batch, 32, *hw)
+    keys = ["layer3d.l19.0.weight", "layer3d.l22.0.weight", "layer3d.l32.0.weight",      # stride 1
+            "layer3d.l21.0.weight", "layer3d.l30.0.weight",                              # stride 2
+            "layer3d.l33.0.weight", "layer3d.l34.0.weight", "layer3d.l36.0.weight",      # transposed + skip
+            "layer3d.l35.1.weight", "layer3d.l36.1.bias",                                # BN before a ReLU + add
+            "layer3d.l37.weight"]      # (l37.bias: the soft-argmin is shift invariant, its gradient is 0)
+    m = model_create_by_name("gcnet", 2 * d2)
+    m.load_state_dict(sd, strict=True)
+    m = m.cuda().train()
+    gfl, gfr = fl.cuda().requires_grad_(True), fr.cuda().requires_grad_(True)
+    glog = _SignLog()
+
+    def hook(out, mode, res=None):
+        out = out.detach()
+        if mode == blocks3d.RELU_BEFORE_ADD and res is not None:
+            d, h, w = out.shape[2:]
+            glog.masks.append((out > res.detach()[:, :, :d, :h, :w]).cpu())
+        else:
+            glog.masks.append((out > 0).cpu())
+
+    blocks3d._TRAIN_RELU_HOOK[0] = hook
+    orig_t = torch.relu
+    torch.relu = glog.wrap(orig_t)                 # (DSM_TRAIN_BN=stock: blocks3d calls torch.relu)
+    try:
+        gcost = m.layer3d.cost(cv.concat_volume(gfl, gfr, d2, False))
+    finally:
+        torch.relu = orig_t
+        blocks3d._TRAIN_RELU_HOOK[0] = None
+    loss = cv.soft_argmin(gcost, None, negate=True).mean()
+    assert len(glog.masks) == 18, len(glog.masks)
+    params = dict(m.named_parameters())
+    ggr = torch.autograd.grad(loss, [params[k] for k in keys] + [gfl, gfr])
+    osd = {k: (v.double().requires_grad_(True) if v.is_floating_point() and "running" not in k
+               else v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    ofl, ofr = fl.double().requires_grad_(True), fr.double().requires_grad_(True)
+    n = OM.Net(osd, training=True)
+    state = {"k": 0, "flips": 0, "units": 0}
+
+    def forced_relu(x, *a, **k):
+        mask = glog.masks[state["k"]]
+        state["k"] += 1
+        own = x.detach() > 0
+        assert mask.shape[:2] == x.shape[:2] and all(a <= b for a, b in zip(mask.shape[2:], x.shape[2:]))
+        d, h, w = mask.shape[2:]
+        state["flips"] += int((own[:, :, :d, :h, :w] != mask).sum())
+        state["units"] += mask.numel()
+        own[:, :, :d, :h, :w] = mask               # outside the skip's corner: no gradient, own sign
+        return x * own.to(x.dtype)
+
+    orig = TF.relu
+    TF.relu = forced_relu                          # the oracle's trunk calls F.relu
+    try:
+        ocost = OM.gcnet_trunk(n, OO.concat_volume(ofl, ofr, d2, False))
+    finally:
+        TF.relu = orig
+    assert state["k"] == 18
+    oloss = OO.soft_argmin(ocost, None, negate=True).mean()
+    ogr = torch.autograd.grad(oloss, [osd[k] for k in keys] + [ofl, ofr])
+    assert tuple(gcost.shape) == tuple(ocost.shape) == (batch, 1, 2 * d2, 2 * hw[0], 2 * hw[1])
+    assert abs(loss.item() - oloss.item()) <= 1e-3 * max(1.0, abs(oloss.item()))
+    assert maxerr(gcost, ocost) <= 2e-5 * ocost.abs().max().item()
+    errs = {k: maxerr(g, r) / max(r.abs().max().item(), 1e-6)
+            for k, g, r in zip(keys + ["fL", "fR"], ggr, ogr)}
+    return errs, state["flips"], state["units"]
+
+
+def test_gcnet_trunk_training_step_vs_oracle(hip_lib):
+    """GCNet's backward against the oracle's float64 autograd with the product's ReLU masks forced: the
+    only user of ReLU-before-add in the BatchNorm backward and of the transposed Cout = 1 head.  Batch 2,
+    odd sizes; weights of stride-1, stride-2 and transposed layers with skip, BN parameters, ``l37``, and
+    both feature inputs at GRAD_TOL."""
+    errs, flips, units = _gcnet_step_errors(83)
+    print({k: "%.1e" % v for k, v in errs.items()})
     _check_gradients(errs, flips, units)
 
 
