@@ -66,6 +66,15 @@ class SelfsupItem(ctypes.Structure):
                 ("pad_", c_int)]
 
 
+class SuplossItem(ctypes.Structure):
+    """struct dsm_suploss_item (include/dsmnet_hip.h), 48 bytes."""
+    _fields_ = [("pred", c_void_p), ("grad", c_void_p), ("B", c_int), ("hc", c_int), ("wc", c_int),
+                ("level", c_int), ("weight", ctypes.c_float), ("pad_", c_int * 3)]
+
+
+DSM_SUPLOSS_MAX_ITEMS = 16
+
+
 class ColorRecord(ctypes.Structure):
     """struct dsm_color_record (include/dsmnet_hip.h)."""
     _fields_ = [("order", c_int * 4), ("jitter", ctypes.c_float * 4), ("flags", c_int), ("alpha_row", c_int)]
@@ -110,6 +119,9 @@ SIGNATURES = {
     "dsm_selfsup_workspace_floats": (c_size_t, [ctypes.POINTER(SelfsupItem), c_int]),
     "dsm_selfsup_fwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
     "dsm_selfsup_bwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
+    "dsm_suploss_workspace_floats": (c_size_t, [c_int] * 5),
+    "dsm_suploss_fwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4),
+    "dsm_suploss_bwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
     "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),
     "dsm_concat_conv_fwd": (c_int, [c_void_p] * 5 + [c_size_t] + [c_void_p] * 2 + [c_int] * 9 + [c_void_p]),
 }

@@ -13,6 +13,7 @@ Reference code each op replaces (sunshinnnn/DSMnet):
   conv3d_block    models/psmnet/submodule.py:16-19, stackhourglass.py:22-62,
                   models/util_conv.py:150-179, models/util_fun.py:41-50
   stereo_color    myTransforms/aug_color.py:28-45, 66-101, 103-203, myTransforms/__init__.py:109-135
+  supervised_pyramid_loss   losses/loss.py:326-338, 407-421, stereo.py:103-113
 """
 import ctypes
 
@@ -419,7 +420,8 @@ def _env_flag(name, default):
 
 
 _OPTIONS = {"fuse_volume": True, "fuse_blocks": True, "conv_precision": _env_precision(), "conv_flags": 0,
-            "separable_volume": _env_flag("DSM_SEPARABLE_VOLUME", True), "separable_flags": 0}
+            "separable_volume": _env_flag("DSM_SEPARABLE_VOLUME", True), "separable_flags": 0,
+            "fused_supervised_loss": _env_flag("DSM_FUSED_SUP_LOSS", True)}
 
 
 def set_option(name, value):
@@ -437,6 +439,8 @@ def set_option(name, value):
     plus a broadcast (``concat_conv_block``) instead of the z-sliding kernel; starts from
     DSM_SEPARABLE_VOLUME=0|1 (default on); ``separable_flags``: raw tuning bits of dsm_concat_conv_fwd;
     ``fuse_blocks`` -- the towers' stride-1 64-channel BasicBlocks run as one launch each (fp16 modes);
+    ``fused_supervised_loss`` -- ``train.losses("supervised")`` runs as ``supervised_pyramid_loss`` (three
+    launches, csrc/suploss.hip) instead of stock torch ops; starts from DSM_FUSED_SUP_LOSS=0|1 (default on);
     ``conv_flags`` -- raw dsm_conv3d_args.flags bits (tile height, grid size)."""
     if name == "conv_fp32":
         old = _OPTIONS["conv_precision"] == "fp32"
@@ -1353,6 +1357,112 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
             "flag_mask": bool(flag_mask)}
     loss, aux = SelfsupPyramidLossFunction.apply(spec, imL, imR_src, imL1, imR1_src, *ds)
     return (loss, aux.view(2 * n, 4)) if return_aux else loss
+
+
+# ----------------------------------------------------------------------------
+# Supervised pyramid loss with D1 / EPE (csrc/suploss.hip)
+# ----------------------------------------------------------------------------
+def supervised_loss_supported(disp_gt, disps, levels):
+    """True when ``supervised_pyramid_loss`` takes these maps: everything CUDA fp32 on one device,
+    gt (B,1,H,W), every prediction (B,[1,]hc,wc) with hc * 2^level >= H and wc * 2^level >= W (the
+    reference's crop then yields the full H x W), at most 16 of them."""
+    if not (torch.is_tensor(disp_gt) and disp_gt.is_cuda and disp_gt.dtype == torch.float32 and disp_gt.dim() == 4
+            and disp_gt.shape[1] == 1 and disp_gt.numel() > 0):
+        return False
+    if not 1 <= len(disps) <= _lib.DSM_SUPLOSS_MAX_ITEMS or len(levels) != len(disps):
+        return False
+    B, _, H, W = disp_gt.shape
+    for d, k in zip(disps, levels):
+        if not (d.is_cuda and d.dtype == torch.float32 and d.device == disp_gt.device and 0 <= int(k) <= 12):
+            return False
+        if d.dim() == 4 and d.shape[1] != 1 or d.dim() not in (3, 4) or d.shape[0] != B or d.numel() == 0:
+            return False
+        if (d.shape[-2] << int(k)) < H or (d.shape[-1] << int(k)) < W:
+            return False
+    return True
+
+
+class SupervisedPyramidLossFunction(torch.autograd.Function):
+    """``spec`` = (levels, weights, flag_smooth); gt and the (B,1,hc,wc) predictions ride as
+    arguments so that autograd sees the predictions."""
+
+    @staticmethod
+    def _items(spec, disps, grads=None):
+        items = (_lib.SuplossItem * len(disps))()
+        for i, d in enumerate(disps):
+            it = items[i]
+            it.pred = d.data_ptr()
+            it.grad = None if grads is None or grads[i] is None else grads[i].data_ptr()
+            it.B, it.hc, it.wc = d.shape[0], d.shape[2], d.shape[3]
+            it.level, it.weight = spec[0][i], spec[1][i]
+        return items
+
+    @staticmethod
+    def forward(ctx, spec, gt, *disps):
+        B, _, H, W = gt.shape
+        n = len(disps)
+        save = any(ctx.needs_input_grad[2:])
+        items = SupervisedPyramidLossFunction._items(spec, disps)
+        lib = _lib.load()
+        nf = lib.dsm_suploss_workspace_floats(n, B, H, W, int(save))
+        if nf == 0:
+            raise ValueError("supervised_pyramid_loss: empty or invalid item list")
+        ws = torch.empty(nf, device=gt.device, dtype=torch.float32)
+        loss = torch.empty((), device=gt.device, dtype=torch.float32)
+        aux = torch.empty(1 + 4 * n, device=gt.device, dtype=torch.float32)
+        coarse = sum(d.numel() for d in disps)
+        with torch.cuda.device(gt.device), _timed("suploss_fwd_tiles+reduce", 4.0 * (n * gt.numel() + coarse + nf)):
+            rc = lib.dsm_suploss_fwd(items, n, _p(gt), H, W, int(spec[2]), int(save), _p(ws), _p(loss),
+                                     _p(aux), _stream())
+        _lib.check(rc, "dsm_suploss_fwd")
+        ctx.spec = spec
+        ctx.save_for_backward(gt, ws, aux, *disps)
+        ctx.mark_non_differentiable(aux)
+        return loss, aux
+
+    @staticmethod
+    def backward(ctx, gloss, gaux):
+        saved = ctx.saved_tensors
+        gt, ws, aux, disps = saved[0], saved[1], saved[2], saved[3:]
+        grads = [torch.empty_like(d) if need else None for d, need in zip(disps, ctx.needs_input_grad[2:])]
+        items = SupervisedPyramidLossFunction._items(ctx.spec, disps, grads)
+        g = gloss.to(torch.float32).contiguous()
+        B, _, H, W = gt.shape
+        work = 4.0 * (sum(gt.numel() + d.numel() for d, gr in zip(disps, grads) if gr is not None))
+        with torch.cuda.device(gt.device), _timed("suploss_bwd_gather", work):
+            rc = _lib.load().dsm_suploss_bwd(items, len(items), _p(gt), H, W, int(ctx.spec[2]), _p(ws),
+                                             _p(aux), _p(g), _stream())
+        _lib.check(rc, "dsm_suploss_bwd")
+        return (None, None) + tuple(grads)
+
+
+def supervised_pyramid_loss(disp_gt, disps, levels, weights, flag_smooth=True):
+    """The reference's supervised objective over a pyramid of outputs, and its accuracy metrics, in
+    two launches forward and one backward (csrc/suploss.hip; losses/loss.py:326-338, 407-421,
+    stereo.py:103-113):
+
+        loss = sum_i weights[i] * loss_supervised(disp_gt, upsample(disps[i], 2**levels[i])[:, :, :H, :W],
+                                                  flag_smooth)
+
+    ``disp_gt`` (B,1,H,W); ``disps[i]`` (B,1,hc,wc) or (B,hc,wc) with hc * 2**levels[i] >= H and
+    wc * 2**levels[i] >= W (``supervised_loss_supported``); at most 16 outputs.  Returns
+    ``(loss, metrics)``: ``metrics`` is the (1 + 4 * len(disps),) device tensor n, then per output
+    L1 mean, smooth mean, EPE and D1 %.  No valid pixel (n == 0): loss 0 with zero gradients, EPE and
+    D1 NaN.  No host synchronisation."""
+    n = len(disps)
+    if n < 1 or not (len(levels) == len(weights) == n):
+        raise ValueError("supervised_pyramid_loss: one level and one weight per prediction")
+    _require_device("supervised_pyramid_loss", disp_gt, *disps)
+    if n > _lib.DSM_SUPLOSS_MAX_ITEMS:
+        raise ValueError("supervised_pyramid_loss: at most %d predictions, got %d" % (_lib.DSM_SUPLOSS_MAX_ITEMS, n))
+    if not supervised_loss_supported(disp_gt, disps, levels):
+        raise ValueError("supervised_pyramid_loss: gt %s with predictions %s at levels %s is not supported "
+                         "(gt (B,1,H,W); every upsampled prediction must cover it)"
+                         % (tuple(disp_gt.shape), [tuple(d.shape) for d in disps], list(levels)))
+    ds = [(d.unsqueeze(1) if d.dim() == 3 else d).contiguous() for d in disps]
+    spec = ([int(k) for k in levels], [float(w) for w in weights], bool(flag_smooth))
+    loss, aux = SupervisedPyramidLossFunction.apply(spec, disp_gt.contiguous(), *ds)
+    return loss, aux
 
 
 # ----------------------------------------------------------------------------

@@ -11,9 +11,15 @@ preset of DSMnet_train_kitti-raw.sh) runs as ONE fused HIP op over the whole pyr
 ``SsSMnet``, ``Cap_ds_lr`` and plain ``depthmono`` (no ``-mask``) are not built.
 
 The forward and backward of the model run on the HIP kernels (``costvolume`` autograd
-functions); the supervised loss itself is a handful of element-wise stock torch ops on
-(B,1,H,W) maps.
+functions).  The supervised objective over the whole pyramid of outputs, together with the D1 /
+EPE of the first output, is ONE fused HIP op as well (``costvolume.supervised_pyramid_loss``,
+csrc/suploss.hip: two launches forward, one backward, no host read in the capturable form) when
+the maps are CUDA float32, the shapes are supported and the option ``fused_supervised_loss`` is
+on (the default; DSM_FUSED_SUP_LOSS=0 turns it off); otherwise -- CPU tensors among them -- it is
+the stock torch restatement below, unchanged.
 """
+import weakref
+
 import torch
 import torch.nn.functional as F
 
@@ -56,6 +62,7 @@ class losses(torch.nn.Module):
         # the loss is then a zero tensor instead of the reference's integer 0 -- what a hipGraph
         # capture of the whole step needs (graphs.GraphedTrainStep sets it)
         self.capturable = False
+        self.last_metrics = None
 
     def Weight_Adjust_levels(self, epoch):
         """Coarse-to-fine: the unit weight slides from the coarsest output (epoch 0) to the
@@ -90,7 +97,38 @@ class losses(torch.nn.Module):
             loss = loss + 0.1 * dxdy[mask].clamp(0, 1).mean()
         return loss
 
+    def _fused_pyramid0(self, disp_gt, disps, scale_disps, flag_smooth):
+        """The weighted outputs through ``costvolume.supervised_pyramid_loss``; ``NotImplemented``
+        when the stock path has to run (CPU or non-fp32 maps, option off, unsupported shapes)."""
+        if not (torch.is_tensor(disp_gt) and disp_gt.is_cuda and self.lossfun == self.loss_supervised):
+            return NotImplemented
+        from . import costvolume as cv
+        if not cv.get_option("fused_supervised_loss"):
+            return NotImplemented
+        picked = [(i, level) for i, level in enumerate(scale_disps) if self.weight_levels[level] > 0]
+        preds = [disps[i] for i, _ in picked]
+        levels = [level for _, level in picked]
+        if not preds or not cv.supervised_loss_supported(disp_gt, preds, levels):
+            return NotImplemented
+        # a level-0 output is used as it is (no crop): it has to be gt's size, as in the stock form
+        if any(level == 0 and p.shape[-2:] != disp_gt.shape[-2:] for p, level in zip(preds, levels)):
+            return NotImplemented
+        loss, aux = cv.supervised_pyramid_loss(disp_gt, preds, levels,
+                                               [self.weight_levels[level] for level in levels], flag_smooth)
+        if picked[0] == (0, 0):
+            # D1 / EPE of the first output ride along.  A weak reference: holding the output itself
+            # would keep this step's whole autograd graph alive until the next call, across a
+            # later hipGraph capture on the same model (graphs.GraphedTrainStep._quiesce)
+            self.last_metrics = (weakref.ref(disps[0]), aux[4], aux[3])
+        if not self.capturable and float(aux[0]) == 0:      # the step's one host read
+            return 0
+        return loss
+
     def losses_pyramid0(self, disp_gt, disps, scale_disps, flag_smooth=False):
+        self.last_metrics = None                # (weak ref to the first output, D1, EPE) of the latest fused call
+        fused = self._fused_pyramid0(disp_gt, disps, scale_disps, flag_smooth)
+        if fused is not NotImplemented:
+            return fused
         _, _, h, w = disp_gt.shape
         loss = 0
         for pred, level in zip(disps, scale_disps):
@@ -205,6 +243,15 @@ def make_optimizer(model, lr=1e-4, betas=(0.9, 0.999)):
     return torch.optim.Adam(model.parameters(), lr=lr, betas=betas)
 
 
+def _metrics(lossfun, disp0, disp_gt):
+    """(D1, EPE) of the first output: what the fused loss of this very call computed along the way,
+    else ``accuracy`` (two more passes over the maps)."""
+    last = getattr(lossfun, "last_metrics", None)
+    if last is not None and last[0]() is disp0:
+        return last[1], last[2]
+    return accuracy(disp0.detach(), disp_gt)
+
+
 def _split(batch):
     if batch.shape[1] < 7:
         raise ValueError("a supervised batch is (B, >=7, H, W): imL | imR | dispL")
@@ -259,7 +306,7 @@ def _train_step(model, optim, lossfun, batch, world):
         if torch.is_tensor(loss):              # the integer 0 when no pixel has ground truth
             loss.backward()
             optim.step()
-    d1, epe = accuracy(dispLs[0].detach(), dispL)
+    d1, epe = _metrics(lossfun, dispLs[0], dispL)
     return float(loss.detach() if torch.is_tensor(loss) else loss), float(d1), float(epe)
 
 
@@ -271,7 +318,7 @@ def validate_step(model, lossfun, batch):
         scale_dispLs, dispLs = model(imL, imR)
         loss = lossfun({"disp_gt": dispL, "disps": dispLs, "scale_disps": scale_dispLs,
                         "flag_smooth": True})
-        d1, epe = accuracy(dispLs[0], dispL)
+        d1, epe = _metrics(lossfun, dispLs[0], dispL)
     return float(loss), float(d1), float(epe)
 
 

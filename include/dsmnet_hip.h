@@ -414,6 +414,47 @@ int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flag_mask, v
 int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flag_mask, const void* workspace,
                     const void* aux, const void* grad_loss, dsm_stream_t stream);
 
+/* (ABI v7, additive) Supervised pyramid loss with the D1 / EPE metrics, fused (csrc/suploss.hip) --
+ * losses/loss.py loss_supervised :326-338 (diff1_dx / diff1_dy :36-44), losses_pyramid0 :407-421,
+ * stereo.py accuracy :103-113.  One item = one weighted output of the model: pred (B,1,hc,wc) fp32
+ * contiguous at pyramid level `level` (scale s = 2^level), its weight, and grad (same shape; NULL =
+ * no gradient wanted).  gt (B,1,H,W) fp32 contiguous is shared by all items.  Per fine pixel:
+ * p = the bilinear sample of F.interpolate(scale_factor=s, align_corners=False) cropped to H x W
+ * (the map itself at level 0), m = gt > 0, dx / dy = forward differences of p, zero in the last
+ * column / row of the cropped image, sm = min(|dx| + |dy|, 1);  n = sum m over the batch and
+ *   loss = sum_items weight * (sum m |gt - p| + 0.1 * flag_smooth * sum m sm) / n    (0 when n == 0).
+ *   dsm_suploss_workspace_floats  n_items * (4 * tiles + (save_for_bwd ? B*H*W : 0)) with
+ *                     tiles = B * ceil(H/16) * ceil(W/64); 0 for invalid arguments
+ *   dsm_suploss_fwd   2 launches (tiles, fixed-order fp64 reduction): loss (1 float) and aux
+ *                     (1 + 4 * n_items floats): n, then per item L1 mean, smooth mean, EPE and D1 %
+ *                     (good pixel: |gt - p| <= 3 OR |gt - p| / gt <= 0.05; EPE = D1 = NaN when n == 0,
+ *                     as accuracy gives).  save_for_bwd: also the unnormalised fine-pixel gradient,
+ *                     4 bytes per pixel per item, into the workspace.
+ *   dsm_suploss_bwd   1 launch, a gather without atomics (bit-reproducible): OVERWRITES grad of
+ *                     every item that has one with d loss / d pred * grad_loss (device scalar);
+ *                     the smoothness adjoint passes where |dx| + |dy| <= 1, sign(0) = 0.
+ *                     workspace and aux are those of the forward (save_for_bwd != 0).
+ * DSM_ERR_ARG (nothing launched): null pointers, n_items outside 1..DSM_SUPLOSS_MAX_ITEMS,
+ * non-positive sizes, items of different B.  DSM_ERR_UNSUPPORTED: hc * s < H or wc * s < W
+ * (the reference's crop would come out smaller than gt), level > 12, B*H*W >= 2^31.
+ * The workspace must be 16-byte aligned (DSM_ERR_ALIGN).  sizeof(dsm_suploss_item) == 48. */
+#define DSM_SUPLOSS_MAX_ITEMS 16
+typedef struct dsm_suploss_item {
+  const void* pred;
+  void* grad;
+  int B, hc, wc, level;
+  float weight;
+  int pad_[3];
+} dsm_suploss_item;
+
+size_t dsm_suploss_workspace_floats(int n_items, int B, int H, int W, int save_for_bwd);
+int dsm_suploss_fwd(const dsm_suploss_item* items, int n_items, const void* gt, int H, int W,
+                    int flag_smooth, int save_for_bwd, void* workspace, void* loss, void* aux,
+                    dsm_stream_t stream);
+int dsm_suploss_bwd(const dsm_suploss_item* items, int n_items, const void* gt, int H, int W,
+                    int flag_smooth, const void* workspace, const void* aux, const void* grad_loss,
+                    dsm_stream_t stream);
+
 /* (ABI v7, additive) Stereo colour augmentation of a training batch, fused -- replaces
  * myTransforms/__init__.py:109-135 Stereo_color / Stereo_normalize applied by Stereo_color_batch,
  * i.e. myTransforms/aug_color.py ColorJitter (RandomOrder :175-203 over Brightness, Contrast,
