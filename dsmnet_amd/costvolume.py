@@ -85,6 +85,43 @@ def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _plan_name(fn, *args):
+    """Branch name written by one of the host-only ``dsm_*_plan`` queries (include/dsmnet_hip.h).  Pointer
+    arguments are tensors, raw addresses or None: only NULL-ness and 16-byte alignment are looked at, so
+    this needs no GPU.  Raises what the launch itself would be refused with."""
+    buf = ctypes.create_string_buffer(96)
+    conv = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+    _lib.check(getattr(_lib.load(), fn)(*(conv + [buf, 96])), fn)
+    return buf.value.decode()
+
+
+def corr1d_plan_name(fL, fR, out, tmp, B, C, H, W, D, stride=1, kernel_size=1):
+    """Kernel(s) ``dsm_corr1d_fwd`` picks (``dsm_corr1d_plan``): ``tile<S,NDH>``, ``fwd<S>vec``,
+    ``fwd<S>scalar`` or ``generic``, with ``+box3`` / ``+box`` when a box filter follows."""
+    return _plan_name("dsm_corr1d_plan", fL, fR, out, tmp, B, C, H, W, D, stride, kernel_size, _lib.DSM_F32)
+
+
+def concat_volume_plan_name(fL, fR, vol, B, C, H, W, D, mask_left, channels_last=True, backward=False):
+    """Kernel ``dsm_concat_volume_fwd`` (``_bwd``: pass gvol, dfL, dfR) picks: ``ndhwc``,
+    ``ndhwc lds>64K``, ``ncdhw vec``, ``ncdhw scalar``; ``ndhwc_bwd``, ``ncdhw_bwd``."""
+    return _plan_name("dsm_concat_volume_bwd_plan" if backward else "dsm_concat_volume_fwd_plan", fL, fR, vol,
+                      B, C, H, W, D, int(mask_left), _lib.DSM_NDHWC if channels_last else _lib.DSM_NCDHW,
+                      _lib.DSM_F32)
+
+
+def soft_argmin_fwd_plan_name(cost, disp, stats, B, Dc, Hc, Wc, D, H, W, negate=False, align_corners=False):
+    """Kernel ``dsm_soft_argmin_fwd`` picks: ``up4<4>``, ``fwd<true,DS>`` or ``fwd<false,DS>``."""
+    return _plan_name("dsm_soft_argmin_fwd_plan", cost, disp, stats, B, Dc, Hc, Wc, D, H, W, int(negate),
+                      int(align_corners), _lib.DSM_F32)
+
+
+def soft_argmin_bwd_plan_name(cost, disp, stats, gdisp, dcost, B, Dc, Hc, Wc, D, H, W, negate=False,
+                              align_corners=False):
+    """Kernel ``dsm_soft_argmin_bwd`` picks: ``bwd_direct``, ``bwd_tile nseg=N`` or ``bwd_fallback``."""
+    return _plan_name("dsm_soft_argmin_bwd_plan", cost, disp, stats, gdisp, dcost, B, Dc, Hc, Wc, D, H, W,
+                      int(negate), int(align_corners), _lib.DSM_F32)
+
+
 def _require_device(name, *tensors):
     for t in tensors:
         if t is None:
@@ -245,9 +282,10 @@ class SoftArgminFunction(torch.autograd.Function):
         need_grad = ctx.needs_input_grad[0]
         stats = torch.empty((B, 2, H, W), device=cost.device, dtype=cost.dtype) if need_grad else None
         lib = _lib.load()
-        # the x4 fast path (soft_argmin.hip: dsm_soft_argmin_fwd) has its own kernel
-        kname = ("soft_argmin_up4_kernel" if (D == 4 * Dc and (Hc, Wc) != (H, W) and not align_corners)
-                 else "soft_argmin_fwd_kernel")
+        # the x4 fast path (soft_argmin.hip: dsm_soft_argmin_fwd) has its own kernel: label the launch
+        # with what the host code picks
+        kname = lambda: soft_argmin_kernel_label(soft_argmin_fwd_plan_name(
+            c4, disp, stats, B, Dc, Hc, Wc, D, H, W, negate, align_corners))
         with torch.cuda.device(cost.device), _timed(kname, 4.0 * B * (Dc * Hc * Wc + H * W)):
             rc = lib.dsm_soft_argmin_fwd(_p(c4), _p(disp), _p(stats), B, Dc, Hc, Wc, D, H, W,
                                          int(negate), int(align_corners), _lib.DSM_F32, _stream())
@@ -269,6 +307,11 @@ class SoftArgminFunction(torch.autograd.Function):
                                          Wc, D, H, W, negate, align, _lib.DSM_F32, _stream())
         _lib.check(rc, "dsm_soft_argmin_bwd")
         return dcost.reshape(shape), None, None, None
+
+
+def soft_argmin_kernel_label(plan):
+    """Timer label of a soft-argmin forward launch from its plan name."""
+    return "soft_argmin_up4_kernel" if plan.startswith("up4") else "soft_argmin_fwd_kernel"
 
 
 def soft_argmin(cost, out_size=None, negate=False, align_corners=False):

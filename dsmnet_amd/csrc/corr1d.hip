@@ -364,25 +364,70 @@ static int check_corr(const void* a, const void* b, const void* c, int B, int C,
   return DSM_OK;
 }
 
-extern "C" int dsm_corr1d_fwd(const void* fL, const void* fR, void* out, void* tmp, int B, int C,
-                              int H, int W, int D, int stride, int ksize, int dtype,
-                              dsm_stream_t stream) {
+// The branch dsm_corr1d_fwd takes: chosen here once, for the launch code and for dsm_corr1d_plan.
+enum { CORR_TILE = 0, CORR_FWD = 1, CORR_GENERIC = 2 };
+enum { CORR_NO_BOX = 0, CORR_BOX3 = 1, CORR_BOX = 2 };
+struct CorrPlan {
+  int kernel;        // CORR_*
+  int ndh;           // tile kernel: d halves (1: D <= 48, 2: D <= 96)
+  int vec;           // 16-byte global accesses (W % 4 == 0 and every pointer aligned)
+  int box;           // CORR_*BOX*: what follows for ksize > 1
+  size_t tile_lds;   // tile kernel: window or reduction bytes, whichever is larger (+ 4096 at launch)
+};
+
+static int pick_corr(const void* fL, const void* fR, const void* out, const void* tmp, int B, int C,
+                     int H, int W, int D, int stride, int ksize, int dtype, CorrPlan* p) {
   int rc = check_corr(fL, fR, out, B, C, H, W, D, stride, ksize, dtype);
   if (rc != DSM_OK) return rc;
   DSM_REQUIRE(ksize == 1 || tmp, DSM_ERR_ARG);
+  const void* raw = ksize > 1 ? tmp : out;
+  const int ndg = (D + DB - 1) / DB;
+  p->vec = (W % 4 == 0) && dsm_aligned16(fL) && dsm_aligned16(fR) && dsm_aligned16(raw);
+  // the tile kernel: the fR window of all channels in LDS at once; D <= 48 with four waves, D <= 96
+  // with eight (two d halves per channel quarter)
+  p->ndh = D <= 48 ? 1 : (D <= 96 ? 2 : 0);
+  const int DP_ = 48 * p->ndh;
+  const size_t win_lds = (size_t)C * (TX + DP_ * stride) * sizeof(float);
+  const size_t red_lds = (size_t)4 * DP_ * (TX + 4) * sizeof(float);
+  p->tile_lds = win_lds > red_lds ? win_lds : red_lds;
+  if (p->vec && p->ndh && C % 16 == 0 && (stride == 1 || stride == 2) && p->tile_lds + 4096 <= 150 * 1024)
+    p->kernel = CORR_TILE;
+  else if ((stride == 1 || stride == 2) && ndg * 16 <= 256)
+    p->kernel = CORR_FWD;
+  else
+    p->kernel = CORR_GENERIC;
+  p->box = ksize == 1 ? CORR_NO_BOX : (ksize == 3 && p->vec && dsm_aligned16(out) ? CORR_BOX3 : CORR_BOX);
+  return DSM_OK;
+}
+
+extern "C" int dsm_corr1d_plan(const void* fL, const void* fR, const void* out, const void* tmp, int B,
+                               int C, int H, int W, int D, int stride, int ksize, int dtype, char* buf,
+                               int len) {
+  DSM_REQUIRE(buf && len > 0, DSM_ERR_ARG);
+  CorrPlan p;
+  int rc = pick_corr(fL, fR, out, tmp, B, C, H, W, D, stride, ksize, dtype, &p);
+  if (rc != DSM_OK) return rc;
+  const char* box = p.box == CORR_BOX3 ? "+box3" : (p.box == CORR_BOX ? "+box" : "");
+  if (p.kernel == CORR_TILE) snprintf(buf, (size_t)len, "tile<%d,%d>%s", stride, p.ndh, box);
+  else if (p.kernel == CORR_FWD) snprintf(buf, (size_t)len, "fwd<%d>%s%s", stride, p.vec ? "vec" : "scalar", box);
+  else snprintf(buf, (size_t)len, "generic%s", box);
+  return DSM_OK;
+}
+
+extern "C" int dsm_corr1d_fwd(const void* fL, const void* fR, void* out, void* tmp, int B, int C,
+                              int H, int W, int D, int stride, int ksize, int dtype,
+                              dsm_stream_t stream) {
+  CorrPlan plan;
+  int rc = pick_corr(fL, fR, out, tmp, B, C, H, W, D, stride, ksize, dtype, &plan);
+  if (rc != DSM_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   dsm_clear_stale_error();
   float* raw = (float*)(ksize > 1 ? tmp : out);
   const int ndg = (D + DB - 1) / DB;
-  const int vec = (W % 4 == 0) && dsm_aligned16(fL) && dsm_aligned16(fR) && dsm_aligned16(raw);
-  // the tile kernel: the fR window of all channels in LDS at once; D <= 48 with four waves, D <= 96
-  // with eight (two d halves per channel quarter)
-  const int NDH_ = D <= 48 ? 1 : (D <= 96 ? 2 : 0);
-  const int DP_ = 48 * NDH_;
-  const size_t win_lds = (size_t)C * (TX + DP_ * stride) * sizeof(float);
-  const size_t red_lds = (size_t)4 * DP_ * (TX + 4) * sizeof(float);
-  const size_t tile_lds = win_lds > red_lds ? win_lds : red_lds;
-  if (vec && NDH_ && C % 16 == 0 && (stride == 1 || stride == 2) && tile_lds + 4096 <= 150 * 1024) {
+  const int vec = plan.vec;
+  const int NDH_ = plan.ndh;
+  const size_t tile_lds = plan.tile_lds;
+  if (plan.kernel == CORR_TILE) {
     dim3 grid(dsm_cdiv(W, TX), H, B);
 #define DSM_CORR_TILE(S_, NDH__)                                                                     \
     do {                                                                                             \
@@ -401,7 +446,7 @@ extern "C" int dsm_corr1d_fwd(const void* fL, const void* fR, void* out, void* t
     else if (NDH_ == 1) DSM_CORR_TILE(2, 1);
     else DSM_CORR_TILE(2, 2);
 #undef DSM_CORR_TILE
-  } else if ((stride == 1 || stride == 2) && ndg * 16 <= 256) {
+  } else if (plan.kernel == CORR_FWD) {
     const int threads = ((ndg * 16 + 63) / 64) * 64;
     const size_t lds = (size_t)CC * (TX + TX + ndg * DB * stride) * sizeof(float);
     dim3 grid(dsm_cdiv(W, TX), H, B);
@@ -416,11 +461,11 @@ extern "C" int dsm_corr1d_fwd(const void* fL, const void* fR, void* out, void* t
     hipLaunchKernelGGL(corr1d_fwd_generic_kernel, grid, dim3(256), 0, s, (const float*)fL,
                        (const float*)fR, raw, C, H, W, D, stride);
   }
-  if (ksize == 3 && vec && dsm_aligned16(out)) {
+  if (plan.box == CORR_BOX3) {
     const long n = (long)B * D * H * (W / 4);
     hipLaunchKernelGGL(box3_kernel, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, (const float*)raw, (float*)out,
                        (long)B * D, H, W);
-  } else if (ksize > 1) {
+  } else if (plan.box == CORR_BOX) {
     dim3 grid(dsm_cdiv(W, 256), H, B * D);
     hipLaunchKernelGGL(box_filter_kernel, grid, dim3(256), 0, s, (const float*)raw, (float*)out,
                        H, W, ksize);

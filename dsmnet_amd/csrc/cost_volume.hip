@@ -214,25 +214,92 @@ static int check_volume_args(const void* a, const void* b, const void* c, int B,
   return DSM_OK;
 }
 
+// The branch dsm_concat_volume_fwd / _bwd takes: chosen here once, for the launch code and for
+// the dsm_concat_volume_*_plan queries.
+enum { VOL_NDHWC = 0, VOL_NDHWC_BIG = 1, VOL_NCDHW_VEC = 2, VOL_NCDHW_SCALAR = 3 };
+constexpr int VOL_TX = 32;
+struct VolPlan {
+  int kind;          // VOL_*
+  size_t lds;        // NDHWC: dynamic LDS bytes
+};
+
+static int pick_volume_fwd(const void* fL, const void* fR, const void* vol, int B, int C, int H, int W,
+                           int D, int mask_left, int layout, int dtype, VolPlan* p) {
+  int rc = check_volume_args(fL, fR, vol, B, C, H, W, D, layout, dtype);
+  if (rc != DSM_OK) return rc;
+  DSM_REQUIRE((mask_left & ~3) == 0, DSM_ERR_ARG);
+  if (mask_left & 2) DSM_REQUIRE(layout == DSM_NDHWC, DSM_ERR_UNSUPPORTED);   // right-referenced: NDHWC forward only
+  p->lds = 0;
+  if (layout == DSM_NDHWC) {
+    DSM_REQUIRE(C % 4 == 0, DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(dsm_aligned16(vol), DSM_ERR_ALIGN);
+    p->lds = (size_t)(VOL_TX + VOL_TX + D - 1) * (C + 4) * sizeof(float);
+    DSM_REQUIRE(p->lds <= 160 * 1024, DSM_ERR_UNSUPPORTED);
+    p->kind = p->lds > 64 * 1024 ? VOL_NDHWC_BIG : VOL_NDHWC;   // past 64 KB the kernel's LDS limit is raised first
+  } else {
+    DSM_REQUIRE((long)B * 2 * C * D < (1L << 31), DSM_ERR_UNSUPPORTED);
+    p->kind = (W % 4 == 0) && dsm_aligned16(vol) ? VOL_NCDHW_VEC : VOL_NCDHW_SCALAR;
+  }
+  return DSM_OK;
+}
+
+static int pick_volume_bwd(const void* gvol, const void* dfL, const void* dfR, int B, int C, int H,
+                           int W, int D, int layout, int dtype, VolPlan* p) {
+  int rc = check_volume_args(gvol, dfL, dfR, B, C, H, W, D, layout, dtype);
+  if (rc != DSM_OK) return rc;
+  p->lds = 0;
+  if (layout == DSM_NDHWC) {
+    DSM_REQUIRE(C % 4 == 0, DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(dsm_aligned16(gvol), DSM_ERR_ALIGN);
+    p->lds = (size_t)2 * C * (VOL_TX + 1) * sizeof(float);
+    DSM_REQUIRE(p->lds <= 64 * 1024, DSM_ERR_UNSUPPORTED);
+    p->kind = VOL_NDHWC;
+  } else {
+    DSM_REQUIRE((long)B * C <= 65535, DSM_ERR_UNSUPPORTED);
+    p->kind = VOL_NCDHW_SCALAR;
+  }
+  return DSM_OK;
+}
+
+extern "C" int dsm_concat_volume_fwd_plan(const void* fL, const void* fR, const void* vol, int B, int C,
+                                          int H, int W, int D, int mask_left, int layout, int dtype,
+                                          char* buf, int len) {
+  DSM_REQUIRE(buf && len > 0, DSM_ERR_ARG);
+  VolPlan p;
+  int rc = pick_volume_fwd(fL, fR, vol, B, C, H, W, D, mask_left, layout, dtype, &p);
+  if (rc != DSM_OK) return rc;
+  static const char* const names[] = {"ndhwc", "ndhwc lds>64K", "ncdhw vec", "ncdhw scalar"};
+  snprintf(buf, (size_t)len, "%s", names[p.kind]);
+  return DSM_OK;
+}
+
+extern "C" int dsm_concat_volume_bwd_plan(const void* gvol, const void* dfL, const void* dfR, int B,
+                                          int C, int H, int W, int D, int mask_left, int layout,
+                                          int dtype, char* buf, int len) {
+  (void)mask_left;
+  DSM_REQUIRE(buf && len > 0, DSM_ERR_ARG);
+  VolPlan p;
+  int rc = pick_volume_bwd(gvol, dfL, dfR, B, C, H, W, D, layout, dtype, &p);
+  if (rc != DSM_OK) return rc;
+  snprintf(buf, (size_t)len, "%s", p.kind == VOL_NDHWC ? "ndhwc_bwd" : "ncdhw_bwd");
+  return DSM_OK;
+}
+
 extern "C" int dsm_concat_volume_fwd(const void* fL, const void* fR, void* vol, int B, int C,
                                      int H, int W, int D, int mask_left, int layout, int dtype,
                                      dsm_stream_t stream) {
-  int rc = check_volume_args(fL, fR, vol, B, C, H, W, D, layout, dtype);
+  VolPlan plan;
+  int rc = pick_volume_fwd(fL, fR, vol, B, C, H, W, D, mask_left, layout, dtype, &plan);
   if (rc != DSM_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   dsm_clear_stale_error();
   const float* l = (const float*)fL;
   const float* r = (const float*)fR;
   float* v = (float*)vol;
-  DSM_REQUIRE((mask_left & ~3) == 0, DSM_ERR_ARG);
-  if (mask_left & 2) DSM_REQUIRE(layout == DSM_NDHWC, DSM_ERR_UNSUPPORTED);   // right-referenced: NDHWC forward only
-  if (layout == DSM_NDHWC) {
-    DSM_REQUIRE(C % 4 == 0, DSM_ERR_UNSUPPORTED);
-    DSM_REQUIRE(dsm_aligned16(vol), DSM_ERR_ALIGN);
-    constexpr int TX = 32;
-    const size_t lds = (size_t)(TX + TX + D - 1) * (C + 4) * sizeof(float);
-    DSM_REQUIRE(lds <= 160 * 1024, DSM_ERR_UNSUPPORTED);
-    if (lds > 64 * 1024 &&
+  if (plan.kind == VOL_NDHWC || plan.kind == VOL_NDHWC_BIG) {
+    constexpr int TX = VOL_TX;
+    const size_t lds = plan.lds;
+    if (plan.kind == VOL_NDHWC_BIG &&
         hipFuncSetAttribute((const void*)volume_ndhwc_fwd_kernel<TX>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return DSM_ERR_LAUNCH;
@@ -240,9 +307,8 @@ extern "C" int dsm_concat_volume_fwd(const void* fL, const void* fR, void* vol, 
     hipLaunchKernelGGL(volume_ndhwc_fwd_kernel<TX>, grid, dim3(256), lds, s, l, r, v, C, H, W, D,
                        mask_left);
   } else {
-    const bool vec = (W % 4 == 0) && dsm_aligned16(vol);
+    const bool vec = plan.kind == VOL_NCDHW_VEC;
     const long planes = (long)B * 2 * C * D;
-    DSM_REQUIRE(planes < (1L << 31), DSM_ERR_UNSUPPORTED);
     const long per = vec ? (long)H * W / 4 : (long)H * W;
     dim3 grid((unsigned)planes, dsm_cdiv(per, 1024), 1);
     if (vec)
@@ -258,21 +324,17 @@ extern "C" int dsm_concat_volume_fwd(const void* fL, const void* fR, void* vol, 
 extern "C" int dsm_concat_volume_bwd(const void* gvol, void* dfL, void* dfR, int B, int C, int H,
                                      int W, int D, int mask_left, int layout, int dtype,
                                      dsm_stream_t stream) {
-  int rc = check_volume_args(gvol, dfL, dfR, B, C, H, W, D, layout, dtype);
+  VolPlan plan;
+  int rc = pick_volume_bwd(gvol, dfL, dfR, B, C, H, W, D, layout, dtype, &plan);
   if (rc != DSM_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   dsm_clear_stale_error();
-  if (layout == DSM_NDHWC) {
-    DSM_REQUIRE(C % 4 == 0, DSM_ERR_UNSUPPORTED);
-    DSM_REQUIRE(dsm_aligned16(gvol), DSM_ERR_ALIGN);
-    constexpr int TX = 32;
-    const size_t lds = (size_t)2 * C * (TX + 1) * sizeof(float);
-    DSM_REQUIRE(lds <= 64 * 1024, DSM_ERR_UNSUPPORTED);
+  if (plan.kind == VOL_NDHWC) {
+    constexpr int TX = VOL_TX;
     dim3 grid(dsm_cdiv(W, TX), H, B);
-    hipLaunchKernelGGL(volume_ndhwc_bwd_kernel<TX>, grid, dim3(256), lds, s, (const float*)gvol,
+    hipLaunchKernelGGL(volume_ndhwc_bwd_kernel<TX>, grid, dim3(256), plan.lds, s, (const float*)gvol,
                        (float*)dfL, (float*)dfR, C, H, W, D, mask_left);
   } else {
-    DSM_REQUIRE((long)B * C <= 65535, DSM_ERR_UNSUPPORTED);
     dim3 grid(dsm_cdiv(W, 256), H, B * C);
     hipLaunchKernelGGL(volume_ncdhw_bwd_kernel, grid, dim3(256), 0, s, (const float*)gvol,
                        (float*)dfL, (float*)dfR, C, H, W, D, mask_left);

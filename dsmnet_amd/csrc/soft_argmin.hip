@@ -445,10 +445,45 @@ static int pick_dsplit(int D) {
   return ds;
 }
 
+// The kernel dsm_soft_argmin_fwd launches: chosen here once, for the launch code and for
+// dsm_soft_argmin_fwd_plan.
+struct SaFwdPlan {
+  int up4;     // the x4 head (soft_argmin_up4_kernel<4>)
+  int up;      // interpolating form of soft_argmin_fwd_kernel
+  int ds;      // lane segments per pixel
+};
+
+static int pick_sa_fwd(const void* cost, const void* disp, int B, int Dc, int Hc, int Wc, int D, int H,
+                       int W, int align_corners, int dtype, SaFwdPlan* p) {
+  int rc = check_sa(cost, disp, B, Dc, Hc, Wc, D, H, W, dtype);
+  if (rc != DSM_OK) return rc;
+  p->up = !(Dc == D && Hc == H && Wc == W);
+  p->ds = pick_dsplit(D);
+  // The x4 head runs with four lane segments only: D == 4 Dc with pick_dsplit(D) == 2 means D == 4,
+  // Dc == 1 < 2, and pick_dsplit(D) == 1 means D < 4, which no multiple of four is -- so Dc >= ds
+  // holds only for Dc >= 4, where ds == 4.  (D == 4 Dc with H, W unchanged still counts as `up`.)
+  p->up4 = p->up && D == 4 * Dc && !align_corners && Dc >= p->ds;
+  return DSM_OK;
+}
+
+extern "C" int dsm_soft_argmin_fwd_plan(const void* cost, const void* disp, const void* stats, int B,
+                                        int Dc, int Hc, int Wc, int D, int H, int W, int negate,
+                                        int align_corners, int dtype, char* buf, int len) {
+  (void)stats; (void)negate;
+  DSM_REQUIRE(buf && len > 0, DSM_ERR_ARG);
+  SaFwdPlan pl;
+  int rc = pick_sa_fwd(cost, disp, B, Dc, Hc, Wc, D, H, W, align_corners, dtype, &pl);
+  if (rc != DSM_OK) return rc;
+  if (pl.up4) snprintf(buf, (size_t)len, "up4<%d>", pl.ds);
+  else snprintf(buf, (size_t)len, "fwd<%s,%d>", pl.up ? "true" : "false", pl.ds);
+  return DSM_OK;
+}
+
 extern "C" int dsm_soft_argmin_fwd(const void* cost, void* disp, void* stats, int B, int Dc,
                                    int Hc, int Wc, int D, int H, int W, int negate,
                                    int align_corners, int dtype, dsm_stream_t stream) {
-  int rc = check_sa(cost, disp, B, Dc, Hc, Wc, D, H, W, dtype);
+  SaFwdPlan pl;
+  int rc = pick_sa_fwd(cost, disp, B, Dc, Hc, Wc, D, H, W, align_corners, dtype, &pl);
   if (rc != DSM_OK) return rc;
   SaParams p;
   p.cost = (const float*)cost; p.disp = (float*)disp; p.stats = (float*)stats;
@@ -456,30 +491,72 @@ extern "C" int dsm_soft_argmin_fwd(const void* cost, void* disp, void* stats, in
   p.sd = src_scale(Dc, D, align_corners); p.sh = src_scale(Hc, H, align_corners);
   p.sw = src_scale(Wc, W, align_corners);
   p.sign = negate ? -1.f : 1.f; p.align = align_corners;
-  const bool up = !(Dc == D && Hc == H && Wc == W);
-  const int ds = pick_dsplit(D);
+  const bool up = pl.up;
+  const int ds = pl.ds;
   const int px_per_block = 4 * (DSM_WAVE / ds);
   dim3 grid(dsm_cdiv(W, px_per_block), H, B), block(256);
   hipStream_t s = (hipStream_t)stream;
   dsm_clear_stale_error();
 #define SA_LAUNCH(UP, DS) hipLaunchKernelGGL((soft_argmin_fwd_kernel<UP, DS>), grid, block, 0, s, p)
-  if (up && D == 4 * Dc && !align_corners && Dc >= ds) {
-    if (ds == 4) hipLaunchKernelGGL(soft_argmin_up4_kernel<4>, grid, block, 0, s, p);
-    else if (ds == 2) hipLaunchKernelGGL(soft_argmin_up4_kernel<2>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(soft_argmin_up4_kernel<1>, grid, block, 0, s, p);
+  if (pl.up4) {
+    DSM_REQUIRE(ds == 4, DSM_ERR_UNSUPPORTED);       // unreachable: see pick_sa_fwd
+    hipLaunchKernelGGL(soft_argmin_up4_kernel<4>, grid, block, 0, s, p);
   } else if (up) { if (ds == 4) SA_LAUNCH(true, 4); else if (ds == 2) SA_LAUNCH(true, 2); else SA_LAUNCH(true, 1); }
   else    { if (ds == 4) SA_LAUNCH(false, 4); else if (ds == 2) SA_LAUNCH(false, 2); else SA_LAUNCH(false, 1); }
 #undef SA_LAUNCH
   return dsm_launch_status();
 }
 
+// The adjoint dsm_soft_argmin_bwd launches: chosen here once, for the launch code and for
+// dsm_soft_argmin_bwd_plan.
+enum { SAB_DIRECT = 0, SAB_TILE = 1, SAB_FALLBACK = 2 };
+struct SaBwdPlan {
+  int kind;          // SAB_*
+  int dseg, nseg;    // tile kernel: disparities per segment, segments
+  long cells;        // tile kernel: bound of the coarse box of a (tile, segment), floats of LDS
+};
+
+static int pick_sa_bwd(const void* cost, const void* disp, const void* stats, const void* gdisp,
+                       const void* dcost, int B, int Dc, int Hc, int Wc, int D, int H, int W,
+                       int align_corners, int dtype, SaBwdPlan* p) {
+  int rc = check_sa(cost, disp, B, Dc, Hc, Wc, D, H, W, dtype);
+  if (rc != DSM_OK) return rc;
+  DSM_REQUIRE(stats && gdisp && dcost, DSM_ERR_ARG);
+  p->kind = SAB_DIRECT; p->dseg = D; p->nseg = 1; p->cells = 0;
+  if (Dc == D && Hc == H && Wc == W) return DSM_OK;
+  const float sd = src_scale(Dc, D, align_corners), sh = src_scale(Hc, H, align_corners);
+  const float sw = src_scale(Wc, W, align_corners);
+  // LDS-tiled adjoint when the tile's coarse box fits (always, when upsampling)
+  int nseg = D >= 96 ? 4 : (D >= 16 ? 2 : 1);
+  p->dseg = dsm_cdiv(D, nseg);
+  p->nseg = dsm_cdiv(D, p->dseg);
+  p->cells = ((long)((SAB_TX - 1) * sw) + 3) * ((long)((SAB_TY - 1) * sh) + 3) *
+             ((long)((p->dseg - 1) * sd) + 3);
+  p->kind = (p->cells * 4 <= 48 * 1024 && (long)B * p->nseg <= 65535) ? SAB_TILE : SAB_FALLBACK;
+  return DSM_OK;
+}
+
+extern "C" int dsm_soft_argmin_bwd_plan(const void* cost, const void* disp, const void* stats,
+                                        const void* gdisp, const void* dcost, int B, int Dc, int Hc,
+                                        int Wc, int D, int H, int W, int negate, int align_corners,
+                                        int dtype, char* buf, int len) {
+  (void)negate;
+  DSM_REQUIRE(buf && len > 0, DSM_ERR_ARG);
+  SaBwdPlan pl;
+  int rc = pick_sa_bwd(cost, disp, stats, gdisp, dcost, B, Dc, Hc, Wc, D, H, W, align_corners, dtype, &pl);
+  if (rc != DSM_OK) return rc;
+  if (pl.kind == SAB_TILE) snprintf(buf, (size_t)len, "bwd_tile nseg=%d", pl.nseg);
+  else snprintf(buf, (size_t)len, "%s", pl.kind == SAB_FALLBACK ? "bwd_fallback" : "bwd_direct");
+  return DSM_OK;
+}
+
 extern "C" int dsm_soft_argmin_bwd(const void* cost, const void* disp, const void* stats,
                                    const void* gdisp, void* dcost, int B, int Dc, int Hc, int Wc,
                                    int D, int H, int W, int negate, int align_corners, int dtype,
                                    dsm_stream_t stream) {
-  int rc = check_sa(cost, disp, B, Dc, Hc, Wc, D, H, W, dtype);
+  SaBwdPlan pl;
+  int rc = pick_sa_bwd(cost, disp, stats, gdisp, dcost, B, Dc, Hc, Wc, D, H, W, align_corners, dtype, &pl);
   if (rc != DSM_OK) return rc;
-  DSM_REQUIRE(stats && gdisp && dcost, DSM_ERR_ARG);
   SaBwdParams p;
   p.cost = (const float*)cost; p.disp = (const float*)disp; p.stats = (const float*)stats;
   p.gdisp = (const float*)gdisp; p.dcost = (float*)dcost;
@@ -487,22 +564,15 @@ extern "C" int dsm_soft_argmin_bwd(const void* cost, const void* disp, const voi
   p.sd = src_scale(Dc, D, align_corners); p.sh = src_scale(Hc, H, align_corners);
   p.sw = src_scale(Wc, W, align_corners);
   p.sign = negate ? -1.f : 1.f; p.align = align_corners;
-  const bool up = !(Dc == D && Hc == H && Wc == W);
   hipStream_t s = (hipStream_t)stream;
   dsm_clear_stale_error();
   dim3 grid(dsm_cdiv(W, 256), H, B), block(256);
-  if (up) {
+  if (pl.kind != SAB_DIRECT) {
     if (hipMemsetAsync(dcost, 0, (size_t)B * Dc * Hc * Wc * sizeof(float), s) != hipSuccess)
       return DSM_ERR_LAUNCH;
-    // LDS-tiled adjoint when the tile's coarse box fits (always, when upsampling)
-    int nseg = D >= 96 ? 4 : (D >= 16 ? 2 : 1);
-    const int dseg = dsm_cdiv(D, nseg);
-    nseg = dsm_cdiv(D, dseg);
-    const long cells = ((long)((SAB_TX - 1) * p.sw) + 3) * ((long)((SAB_TY - 1) * p.sh) + 3) *
-                       ((long)((dseg - 1) * p.sd) + 3);
-    if (cells * 4 <= 48 * 1024 && (long)B * nseg <= 65535) {
-      dim3 tgrid(dsm_cdiv(W, SAB_TX), dsm_cdiv(H, SAB_TY), B * nseg);
-      hipLaunchKernelGGL(soft_argmin_bwd_tile_kernel, tgrid, block, (size_t)cells * 4, s, p, dseg, nseg);
+    if (pl.kind == SAB_TILE) {
+      dim3 tgrid(dsm_cdiv(W, SAB_TX), dsm_cdiv(H, SAB_TY), B * pl.nseg);
+      hipLaunchKernelGGL(soft_argmin_bwd_tile_kernel, tgrid, block, (size_t)pl.cells * 4, s, p, pl.dseg, pl.nseg);
       return dsm_launch_status();
     }
     hipLaunchKernelGGL(soft_argmin_bwd_kernel<true>, grid, block, 0, s, p);

@@ -60,6 +60,24 @@ int dsm_corr1d_fwd(const void* fL, const void* fR, void* out, void* tmp,
                    int B, int C, int H, int W, int D, int stride, int ksize,
                    int dtype, dsm_stream_t stream);
 
+/* (ABI v7, additive) Host-only plan queries of the ops that choose between several kernels.  Each
+ * takes the arguments of the entry point it describes (the stream replaced by buf, len), runs the
+ * SAME selection code as the launch, returns the SAME error codes the launch would return, and
+ * writes the NUL-terminated name of the chosen branch into buf[len].  Pointers are inspected for
+ * NULL and 16-byte alignment only, never dereferenced: no launch, no device access, no GPU needed.
+ *
+ * dsm_corr1d_plan:  "tile<S,NDH>"  the all-channels-in-LDS tile kernel (S = stride 1 | 2; NDH = 1 for
+ *                                  D <= 48, 2 for D <= 96); needs 16-byte accesses, C % 16 == 0 and
+ *                                  a window of at most 150 KB - 4 KB of LDS;
+ *                   "fwd<S>vec" / "fwd<S>scalar"  the chunked kernel (stride 1 | 2, D <= 128), with
+ *                                  16-byte or scalar global accesses (W % 4 != 0 or a pointer that
+ *                                  is not 16-byte aligned: scalar);
+ *                   "generic"      one thread per output (any other stride, D > 128);
+ *   followed by "+box3" (ksize 3, 16-byte accesses) or "+box" (any other ksize > 1). */
+int dsm_corr1d_plan(const void* fL, const void* fR, const void* out, const void* tmp,
+                    int B, int C, int H, int W, int D, int stride, int ksize,
+                    int dtype, char* buf, int len);
+
 /* grad_out: (B,D,H,W); dfL, dfR: (B,C,H,W), fully overwritten.
  * tmp: (B,D,H,W) scratch, needed iff ksize > 1. */
 int dsm_corr1d_bwd(const void* grad_out, const void* fL, const void* fR,
@@ -87,6 +105,17 @@ int dsm_concat_volume_bwd(const void* gvol, void* dfL, void* dfR,
                           int B, int C, int H, int W, int D,
                           int mask_left, int layout, int dtype, dsm_stream_t stream);
 
+/* (ABI v7, additive) Plan queries (see dsm_corr1d_plan).  Forward: "ndhwc", "ndhwc lds>64K" (the
+ * staged rows need more than 64 KB of LDS: the kernel's limit is raised first; more than 160 KB is
+ * DSM_ERR_UNSUPPORTED), "ncdhw vec" (W % 4 == 0 and vol 16-byte aligned), "ncdhw scalar".
+ * Backward: "ndhwc_bwd", "ncdhw_bwd". */
+int dsm_concat_volume_fwd_plan(const void* fL, const void* fR, const void* vol,
+                               int B, int C, int H, int W, int D,
+                               int mask_left, int layout, int dtype, char* buf, int len);
+int dsm_concat_volume_bwd_plan(const void* gvol, const void* dfL, const void* dfR,
+                               int B, int C, int H, int W, int D,
+                               int mask_left, int layout, int dtype, char* buf, int len);
+
 /* ---------------------------------------------------------------------------
  * (a6,a7) soft-argmin disparity regression, fused.  Replaces
  *   PSMNet: F.upsample(trilinear) -> F.softmax -> disparityregression
@@ -110,6 +139,20 @@ int dsm_soft_argmin_bwd(const void* cost, const void* disp, const void* stats,
                         const void* gdisp, void* dcost,
                         int B, int Dc, int Hc, int Wc, int D, int H, int W,
                         int negate, int align_corners, int dtype, dsm_stream_t stream);
+
+/* (ABI v7, additive) Plan queries (see dsm_corr1d_plan).  Forward: "up4<4>" (the x4 head: D == 4 Dc,
+ * align_corners = 0, Dc >= 4), "fwd<true,DS>" (interpolating) or "fwd<false,DS>" (GCNet form) with
+ * DS = 4 | 2 | 1 lane segments per pixel (D >= 8 | D >= 4 | D < 4).  Backward: "bwd_direct" (no
+ * interpolation), "bwd_tile nseg=N" (the LDS-tiled adjoint; N = 1 | 2 | 4 disparity segments for
+ * D < 16 | D < 96 | D >= 96), "bwd_fallback" (per-pixel global atomics: the coarse box of a 32 x 8
+ * tile needs more than 48 KB of LDS -- down-sampling -- or B * N > 65535). */
+int dsm_soft_argmin_fwd_plan(const void* cost, const void* disp, const void* stats,
+                             int B, int Dc, int Hc, int Wc, int D, int H, int W,
+                             int negate, int align_corners, int dtype, char* buf, int len);
+int dsm_soft_argmin_bwd_plan(const void* cost, const void* disp, const void* stats,
+                             const void* gdisp, const void* dcost,
+                             int B, int Dc, int Hc, int Wc, int D, int H, int W,
+                             int negate, int align_corners, int dtype, char* buf, int len);
 
 /* ---------------------------------------------------------------------------
  * (a4,a5) 3-D convolution block, k = 3, fused epilogue.  Replaces
