@@ -19,6 +19,7 @@ DSM_NCDHW, DSM_NDHWC = 0, 1
 DSM_CONV_FP32_MFMA, DSM_CONV_COUT1_CHUNKED, DSM_CONV_TM_SHIFT, DSM_CONV_BLOCKS_SHIFT = 1, 2, 4, 16
 DSM_CONV_NO_NSPLIT = 4
 DSM_CONV_NO_ONCE = 8
+DSM_CONV_KSPLIT_SHIFT = 8
 DSM_PREC_F32, DSM_PREC_F16, DSM_PREC_F16X2 = 0, 1, 2
 
 
@@ -44,7 +45,8 @@ class Conv3dArgs(ctypes.Structure):
                 ("stride", c_int), ("transposed", c_int), ("relu", c_int),
                 ("kd", c_int), ("k", c_int), ("dil", c_int),
                 ("flags", c_int), ("precision", c_int), ("x_amax", c_void_p), ("y_amax", c_void_p),
-                ("vol_virtual", c_int), ("vol_mask_left", c_int)]
+                ("vol_virtual", c_int), ("vol_mask_left", c_int),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
 class BasicBlock2dArgs(ctypes.Structure):
@@ -106,6 +108,7 @@ SIGNATURES = {
     "dsm_conv3d_fwd": (c_int, [ctypes.POINTER(Conv3dArgs), c_void_p]),
     "dsm_basicblock2d_fwd": (c_int, [ctypes.POINTER(BasicBlock2dArgs), c_void_p]),
     "dsm_conv3d_plan": (c_int, [ctypes.POINTER(Conv3dArgs), ctypes.c_char_p, c_int]),
+    "dsm_conv3d_workspace_bytes": (c_size_t, [ctypes.POINTER(Conv3dArgs)]),
     "dsm_conv3d_wgrad": (c_int, [c_void_p] * 4 + [c_int] * 12 + [c_void_p] * 3),
     "dsm_conv2d_wgrad": (c_int, [c_void_p] * 4 + [c_int] * 11 + [c_void_p] * 3),
     "dsm_conv3d_cout1_bwd": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),

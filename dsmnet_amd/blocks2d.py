@@ -62,6 +62,8 @@ def fused_ok(conv, x):
         return False
     if p[0] != d[0] * (k[0] - 1) // 2 or conv.padding_mode != "zeros":
         return False
+    if conv.out_channels in cv.WIDE2D_COUT:
+        return _wide_ok(conv, x)
     if conv.out_channels not in (32, 64, 128):
         return False
     cin = x.shape[1]
@@ -71,6 +73,26 @@ def fused_ok(conv, x):
     key = (s[0], conv.out_channels // 32, k[0], d[0])
     return key in {(1, 1, 3, 1), (1, 2, 3, 1), (1, 4, 3, 1), (1, 4, 3, 2), (2, 1, 3, 1),
                    (2, 2, 3, 1), (1, 1, 1, 1), (1, 4, 1, 1), (2, 2, 1, 1)}
+
+
+# wide layers profiles/wide2d.md measured slower than the stock layer: (Cin, Cout, stride)
+_WIDE2D_EXCLUDED = frozenset()
+
+
+def _wide_ok(conv, x):
+    """The wide 3x3 layers (256 / 512 / 1024 outputs; csrc/conv_wide2d.hpp, plan kind 8 of
+    ``dsm_conv3d_fwd``): k3, dilation 1, stride 1 or 2, Cin % 16 == 0, an fp16 precision mode (under
+    "bf16x3" / "fp32" the plan refuses and the caller keeps the stock layer), 32-bit offsets."""
+    if conv.kernel_size[0] != 3 or conv.dilation[0] != 1 or cv.get_option("conv_precision") not in ("f16x2", "f16"):
+        return False
+    B, cin, H, W = x.shape
+    s = conv.stride[0]
+    if cin % 16 != 0 or cin != conv.in_channels or (cin, conv.out_channels, s) in _WIDE2D_EXCLUDED:
+        return False
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    if Wo > (2032 if s == 1 else 1016) or B * Ho * Wo >= 2 ** 20:     # eight column blocks of one staged box at most
+        return False
+    return 4 * B * cin * H * W < 2 ** 31 and B * Ho * Wo * conv.out_channels < 2 ** 31 - 1
 
 
 class _Folded2d(object):

@@ -462,9 +462,14 @@ def _env_flag(name, default):
     return default if v == "" else v == "1"
 
 
+# ``wide_conv2d``: default from profiles/wide2d.md, whole DispNetC forward, option off
+# against on in one process
+_WIDE_CONV2D_DEFAULT = False
+
 _OPTIONS = {"fuse_volume": True, "fuse_blocks": True, "conv_precision": _env_precision(), "conv_flags": 0,
             "separable_volume": _env_flag("DSM_SEPARABLE_VOLUME", True), "separable_flags": 0,
-            "fused_supervised_loss": _env_flag("DSM_FUSED_SUP_LOSS", True)}
+            "fused_supervised_loss": _env_flag("DSM_FUSED_SUP_LOSS", True),
+            "wide_conv2d": _env_flag("DSM_WIDE_CONV2D", _WIDE_CONV2D_DEFAULT)}
 
 
 def set_option(name, value):
@@ -484,7 +489,10 @@ def set_option(name, value):
     ``fuse_blocks`` -- the towers' stride-1 64-channel BasicBlocks run as one launch each (fp16 modes);
     ``fused_supervised_loss`` -- ``train.losses("supervised")`` runs as ``supervised_pyramid_loss`` (three
     launches, csrc/suploss.hip) instead of stock torch ops; starts from DSM_FUSED_SUP_LOSS=0|1 (default on);
-    ``conv_flags`` -- raw dsm_conv3d_args.flags bits (tile height, grid size)."""
+    ``wide_conv2d`` -- the 256 / 512 / 1024-channel 3x3 layers of the DispNetC / iResNet encoders run on the
+    wide MFMA kernel (csrc/conv_wide2d.hpp; eval, fp16 modes) instead of the stock layer; starts from
+    DSM_WIDE_CONV2D=0|1;
+    ``conv_flags`` -- raw dsm_conv3d_args.flags bits (tile height, grid size, K-ranges of the wide layers)."""
     if name == "conv_fp32":
         old = _OPTIONS["conv_precision"] == "fp32"
         _OPTIONS["conv_precision"] = "fp32" if value else "bf16x3"
@@ -604,11 +612,16 @@ def carry_amax(dst, *srcs):
     return dst
 
 
+WIDE2D_COUT = (256, 512, 1024)
+
+
 def _split_kernel_layer(a):
     """Does ``dsm_conv3d_fwd`` run this layer on a split-operand kernel (conv3d.hip make_plan kinds
     5 / 6)?  3x3(x3) taps, Cin % 16 == 0, Cout a multiple of 32 up to 64 (3-D; 128 on small volumes at
     stride 1) / 128 (2-D); stride 1, 3-D stride 2 to 64 channels, or transposed from Cin % 32 == 0."""
     kd, k = (a.kd or 3), (a.k or 3)
+    if kd == 1 and k == 3 and a.Cin % 16 == 0 and a.Cout in WIDE2D_COUT:       # conv_wide2d.hpp (plan kind 8)
+        return not a.transposed and (a.dil or 1) == 1
     if k != 3 or a.Cin % 16 or a.Cout % 32 or a.Cout > 128:
         return False
     if kd == 3 and a.Cout == 128:                    # four workgroup columns of 32: small volumes, stride 1 only
@@ -787,11 +800,19 @@ def conv2d_block(x, packed_weight, cout, scale=None, shift=None, residual=None, 
     a.kd, a.k, a.dil = 1, int(k), int(dilation)
     a.flags = _conv_flags()
     keep = _set_precision(a, x, y)
+    ws = None
+    if cout in WIDE2D_COUT:
+        # the wide layers' K-split partial sums: from torch's caching allocator, per call (no
+        # synchronisation; inside a hipGraph capture the block belongs to the graph's pool)
+        nws = _lib.load().dsm_conv3d_workspace_bytes(ctypes.byref(a))
+        if nws:
+            ws = torch.empty(nws // 4, device=dev, dtype=torch.float32)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), nws
     work = 2.0 * k * k * cin * cout * B * Ho * Wo
     with torch.cuda.device(dev), _timed(lambda: conv3d_plan_name(a), work):
         rc = _lib.load().dsm_conv3d_fwd(ctypes.byref(a), _stream())
     _lib.check(rc, "dsm_conv3d_fwd")
-    del keep
+    del keep, ws
     return y
 
 

@@ -39,6 +39,7 @@ def build(force=False, verbose=True, stamps=False):
         subprocess.run(cmd, check=True)
         return lib
     hdrs = [os.path.join(HERE, "common.hpp"), os.path.join(HERE, "conv_split.hpp"), os.path.join(HERE, "conv_zs.hpp"), os.path.join(HERE, "deconv_zs.hpp"), os.path.join(HERE, "conv_common.hpp"),
+            os.path.join(HERE, "basicblock2d.hpp"), os.path.join(HERE, "conv_wide2d.hpp"),
             os.path.join(HERE, "..", "..", "include", "dsmnet_hip.h")]
     srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
     objs = []

@@ -874,8 +874,14 @@ size_t bf16x3_section_bytes(int Cin, int Cout, int kd, int k) {
 }
 // Section 3 (same shapes): a 16-byte header {absolute maximum of the weights, 0, 0, 0} followed by
 // the two fp16 planes of w * 2^ew (conv_split.hpp, PM = 2 | 1).
+// The wide 2-D layers (Cout 256 / 512 / 1024; conv_wide2d.hpp, fp16 modes only) carry section 3 WITHOUT a
+// section 2.
+bool wide2d_layer(int Cin, int Cout, int kd, int k) {
+  return kd == 1 && k == 3 && Cin % 16 == 0 && (Cout == 256 || Cout == 512 || Cout == 1024);
+}
 size_t f16_section_bytes(int Cin, int Cout, int kd, int k) {
-  return bf16x3_section_bytes(Cin, Cout, kd, k) ? 16 + (size_t)Cin * Cout * kd * 9 * 4 : 0;
+  return (bf16x3_section_bytes(Cin, Cout, kd, k) || wide2d_layer(Cin, Cout, kd, k))
+             ? 16 + (size_t)Cin * Cout * kd * 9 * 4 : 0;
 }
 
 // Conv3d(k3, s1) to 32 channels from Cin % 32 == 0 runs on the z-sliding kernel (conv_zs.hpp):
@@ -889,11 +895,13 @@ int pack_split_sections(const float* w, char* frag, int Cin_src, int Cin, int Co
                         int transposed, hipStream_t s) {
   const int ntaps = kd * k * k;
   const long n = (long)Cin * Cout * ntaps;
-  if (!bf16x3_section_bytes(Cin, Cout, kd, k)) return DSM_OK;
+  if (!f16_section_bytes(Cin, Cout, kd, k)) return DSM_OK;
+  const bool has2 = bf16x3_section_bytes(Cin, Cout, kd, k) != 0;
   char* sec2 = frag + n * 4;
   char* sec3 = sec2 + bf16x3_section_bytes(Cin, Cout, kd, k);
   const bool zs = zs_layer(Cin, Cout, kd, k, transposed) && Cin_src == Cin;
-  if (zs)
+  if (!has2) {}
+  else if (zs)
     hipLaunchKernelGGL(pack_weights_zs_kernel<3>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, w,
                        (unsigned short*)sec2, (const float*)nullptr, Cin);
   else
@@ -989,6 +997,32 @@ extern "C" size_t dsm_conv_packed_weight_bytes(int Cin, int Cout, int kd, int k)
 
 namespace {
 
+// Work decomposition of a wide 2-D layer (conv_wide2d.hpp), a pure function of the arguments: M-block,
+// N-column width (64, or 32 where 64-wide columns cannot give every CU a workgroup), K-ranges.
+// flags bits 8..13 force the number of K-ranges (clamped to the 16-channel chunks there are).
+bool wide2d_units(const dsm_conv3d_args* a, WideParams* w) {
+  w->B = a->B; w->Cin = a->Cin; w->Cout = a->Cout; w->Hi = a->Hi; w->Wi = a->Wi; w->Ho = a->Ho; w->Wo = a->Wo;
+  w->S = a->stride;
+  if (!dsmk::wide2d_geometry(*w)) return false;
+  // at most eight chunks (216 MFMA roundings of the fp32 accumulator) per range: the tower layers hold the
+  // f16x2 error band with chains of 540; a 64-chunk chain (conv6b unsplit, 1,728) would leave it
+  const int nch = a->Cin / 16, kmax = nch < 16 ? nch : 16, kmin = (nch + 7) / 8;
+  if (kmin > 63) return false;
+  const long mblocks = (long)a->B * w->nby * w->nbx;
+  if (mblocks >= (1l << 20)) return false;
+  w->nwn = (mblocks * (a->Cout / 64) * kmax >= 256) ? 2 : 1;
+  w->ncol = a->Cout / (32 * w->nwn);
+  const long units = mblocks * w->ncol;
+  int ks = (int)((256 + units - 1) / units);
+  if (ks > kmax) ks = kmax;
+  const int forced = (a->flags >> DSM_CONV_KSPLIT_SHIFT) & 0x3f;
+  if (forced) ks = forced < nch ? forced : nch;
+  if (ks < kmin) ks = kmin;
+  w->ksplit = ks;
+  w->nunits = (int)(units * ks);
+  return true;
+}
+
 int make_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
   DSM_REQUIRE(a && a->x && a->w_packed && a->y, DSM_ERR_ARG);
   DSM_REQUIRE(a->B > 0 && a->Cin > 0 && a->Cout > 0, DSM_ERR_ARG);
@@ -1022,6 +1056,20 @@ int make_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
       const bool zslide = !(a->flags & DSM_CONV_COUT1_CHUNKED);      // A/B runs: the chunked kernel
       *pl = Plan{(a->Cin == 32 && zslide) ? 4 : 2, 1, 0, 0, 8, 3, 3, 1};
     }
+    return DSM_OK;
+  }
+  if (a->Cout == 256 || a->Cout == 512 || a->Cout == 1024) {
+    // the wide 2-D layers (DispNetC / iResNet encoder): conv_wide2d.hpp, fp16 modes only, no skip input,
+    // the natural output size; 32-bit offsets with the out-of-range marker at 2^31
+    DSM_REQUIRE(wide2d_layer(a->Cin, a->Cout, kd, k) && dil == 1 && !a->transposed && !a->vol_virtual &&
+                !a->residual && a->Ho == nH && a->Wo == nW, DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(a->precision != DSM_PREC_F32 && bf16x3_enabled(a), DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(4ul * a->B * a->Hi * a->Wi * a->Cin < 0x80000000ul &&
+                (unsigned long)a->B * a->Ho * a->Wo * a->Cout < 0x7fffffffUL, DSM_ERR_UNSUPPORTED);
+    WideParams w;
+    DSM_REQUIRE(wide2d_units(a, &w), DSM_ERR_UNSUPPORTED);
+    *pl = Plan{8, a->stride, w.nwn, w.nunits, 16, 1, 3, 1};      // (TM: the work units)
+    pl->nsplit = w.ksplit;
     return DSM_OK;
   }
   DSM_REQUIRE(a->Cout == 32 || a->Cout == 64 || a->Cout == 128, DSM_ERR_UNSUPPORTED);
@@ -1118,7 +1166,7 @@ int make_plan(const dsm_conv3d_args* a, Plan* pl) {
   const int rc = make_plan_f32(a, pl);
   if (rc != DSM_OK) return rc;
   pl->pm = 3;
-  if ((pl->kind == 5 || pl->kind == 6 || pl->kind == 7) && a->precision != DSM_PREC_F32) {
+  if ((pl->kind == 5 || pl->kind == 6 || pl->kind == 7 || pl->kind == 8) && a->precision != DSM_PREC_F32) {
     DSM_REQUIRE(a->x_amax != nullptr, DSM_ERR_ARG);      // the input's absolute maximum (device scalar)
     pl->pm = a->precision == DSM_PREC_F16X2 ? 2 : 1;
   }
@@ -1156,6 +1204,7 @@ extern "C" int dsm_conv3d_plan(const dsm_conv3d_args* a, char* buf, int len) {
       else snprintf(buf, len, "conv2d_%s_mfma_kernel<NT=%d,TM=%d,DIL=%d>", pr, pl.NT, pl.TM, pl.DIL);
       break;
     }
+    case 8: snprintf(buf, len, "conv2d_wide_%s_mfma_kernel<S=%d,N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", pl.S, 32 * pl.NT, pl.nsplit, pl.TM); break;
     case 7: snprintf(buf, len, "conv3d_zs_%s_mfma_kernel%s", pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), a->vol_virtual ? "<vol>" : ""); break;
     case 6: snprintf(buf, len, "deconv3d_%s%s_mfma_kernel<NT=%d>", pl.zs ? "zs_" : "",
                      pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), pl.NT); break;
@@ -1188,10 +1237,34 @@ extern "C" int dsm_basicblock2d_fwd(const dsm_basicblock2d_args* a, dsm_stream_t
   return dsmk::run_basicblock_f16(a->precision == DSM_PREC_F16X2 ? 2 : 1, p, (hipStream_t)stream);
 }
 
+extern "C" size_t dsm_conv3d_workspace_bytes(const dsm_conv3d_args* a) {
+  Plan pl;
+  if (make_plan_f32(a, &pl) != DSM_OK || pl.kind != 8 || pl.nsplit <= 1) return 0;
+  return (size_t)pl.nsplit * a->B * a->Ho * a->Wo * a->Cout * sizeof(float);
+}
+
 extern "C" int dsm_conv3d_fwd(const dsm_conv3d_args* a, dsm_stream_t stream) {
   Plan pl;
   int rc = make_plan(a, &pl);
   if (rc != DSM_OK) return rc;
+  if (pl.kind == 8) {
+    WideParams w;
+    wide2d_units(a, &w);
+    const size_t need = dsm_conv3d_workspace_bytes(a);
+    DSM_REQUIRE(need == 0 || (a->workspace && a->workspace_bytes >= need), DSM_ERR_ARG);
+    DSM_REQUIRE(need == 0 || dsm_aligned16(a->workspace), DSM_ERR_ALIGN);
+    DSM_REQUIRE(a->relu == 0 || a->relu == 1 || a->relu == 2, DSM_ERR_ARG);
+    const char* sec3 = (const char*)a->w_packed + (size_t)a->Cin * a->Cout * 9 * 4;
+    w.x = (const float*)a->x; w.w = (const unsigned char*)(sec3 + 16); w.w_amax = (const float*)sec3;
+    w.scale = a->scale; w.shift = a->shift; w.y = (float*)a->y; w.ws = (float*)a->workspace;
+    w.x_amax = a->x_amax; w.y_amax = a->y_amax; w.relu = a->relu ? 1 : 0;
+    w.xbytes = (unsigned)(4ul * a->B * a->Hi * a->Wi * a->Cin);
+    w.wbytes = (unsigned)((size_t)a->Cin * a->Cout * 9 * 4);
+    int grid = (a->flags >> DSM_CONV_BLOCKS_SHIFT) & 0xffff;      // forced grid: the units are walked in a loop
+    if (grid <= 0 || grid > w.nunits) grid = w.nunits;
+    dsm_clear_stale_error();
+    return dsmk::run_wide2d_f16(pl.pm, w, grid, (hipStream_t)stream);
+  }
   ConvParams p;
   p.x = (const float*)a->x; p.w = (const float*)a->w_packed; p.scale = a->scale;
   p.x_amax = a->x_amax; p.w_amax = nullptr; p.y_amax = a->y_amax;

@@ -26,7 +26,7 @@ struct ConvParams {
 
 // One place decides the kernel variant; dsm_conv3d_fwd launches it, dsm_conv3d_plan names it.
 // kind: 0 conv, 1 deconv, 2 conv cout1, 3 deconv cout1, 4 conv cout1 z-sliding, 5 conv split (bf16x3 / f16x2 / f16), 6 deconv split,
-//       7 z-sliding conv (Cout = 32, stride 1; conv_zs.hpp)
+//       7 z-sliding conv (Cout = 32, stride 1; conv_zs.hpp), 8 wide 2-D conv (Cout 256 / 512 / 1024; conv_wide2d.hpp)
 // zs (kind 6, fp16 modes): the z-sliding transposed convolution (deconv_zs.hpp) instead of deconv_split_kernel
 struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int pm = 3; int once = 0; int zs = 0; };
 
@@ -68,6 +68,49 @@ struct BbParams {
 
 __attribute__((visibility("hidden"))) int run_basicblock_f16(int pm, const BbParams& p, hipStream_t s);
 
+// the wide 2-D convolution (conv_wide2d.hpp, plan kind 8): Cout = 256 | 512 | 1024, fp16 modes
+constexpr int WIDE_SLOTS = 768;     // LDS voxel slots of one staged input box
+constexpr int WIDE_PIXELS = 512;    // output pixels of an M-block: 8 waves x 4 M-tiles of 32 / 2 output blocks
+struct WideParams {
+  const float* x;
+  const unsigned char* w;       // the packed f16 section past its header
+  const float* scale; const float* shift;
+  float* y;
+  float* ws;                    // [ksplit][B*Ho*Wo][Cout] partial sums (ksplit > 1)
+  const float* x_amax; const float* w_amax; float* y_amax;
+  int B, Cin, Cout, Hi, Wi, Ho, Wo, S, relu;
+  int R, CW, nby, nbx;          // M-block: R output rows x CW columns; blocks per image
+  int IY, IX, XP, XE;           // input box rows / columns, LDS row pitch in slots, even-column count (S = 2)
+  int nwn, ncol;                // 32-channel output blocks per workgroup (2 | 1), N-columns = Cout / (32 nwn)
+  int ksplit, nunits;
+  unsigned xbytes, wbytes;
+};
+// M-block of a layer: the (R, CW) with the fewest rounds of M-tiles (a round = one M-tile on each of four
+// wave groups), then the fewest blocks, among column splits nbx = 1 .. 8.  False: no block fits.
+inline bool wide2d_geometry(WideParams& p) {
+  long best = -1;
+  for (int nbx = 1; nbx <= 8; ++nbx) {
+    const int CW = (p.Wo + nbx - 1) / nbx;
+    const int IX = (CW - 1) * p.S + 3, XE = (IX + 1) / 2, XP = p.S == 1 ? IX : 2 * XE;
+    if (CW > WIDE_PIXELS || 3 * XP > WIDE_SLOTS) continue;
+    int R = WIDE_PIXELS / CW;
+    const int rl = (WIDE_SLOTS / XP - 3) / p.S + 1;
+    if (rl < R) R = rl;
+    if (p.Ho < R) R = p.Ho;
+    const int nby = (p.Ho + R - 1) / R;
+    R = (p.Ho + nby - 1) / nby;
+    const int tiles = (R * CW + 31) / 32;
+    const long cost = (long)nbx * nby * ((tiles + 3) / 4) * 1024 + nbx * nby;
+    if (best < 0 || cost < best) {
+      best = cost;
+      p.R = R; p.CW = CW; p.nbx = nbx; p.nby = nby;
+      p.IY = (R - 1) * p.S + 3; p.IX = IX; p.XP = XP; p.XE = XE;
+    }
+  }
+  return best >= 0;
+}
+__attribute__((visibility("hidden"))) int run_wide2d_f16(int pm, const WideParams& p, int grid, hipStream_t s);
+
 }  // namespace dsmk
 
 namespace {
@@ -76,6 +119,7 @@ using dsmk::ConvParams;
 using dsmk::Plan;
 using dsmk::ZsParams;
 using dsmk::BbParams;
+using dsmk::WideParams;
 
 // Compile-time loop: f(integral_constant<int, I>) for I in [I0, N).  Used where an index must
 // be a constant expression so that accumulator arrays stay in registers (a runtime-indexed

@@ -5,6 +5,8 @@
 //   f16:   operands rounded to fp16, fp32 accumulate -- the reduced-precision mode of BASELINE
 //          config #5 ("PSMNet fp16 training step"); the reference itself computes in fp32
 //          (models/psmnet/stackhourglass.py:124).
+// Also here: the wide 2-D layers of the DispNetC / iResNet encoder (conv_wide2d.hpp: Cout 256 / 512 / 1024,
+// models/dispnetcorr.py conv3b .. conv6b), which exist in the fp16 modes only.
 // Replaces the same reference code as conv3d.hip: convbn_3d / conv3d_bn / deconv3d_bn and the
 // towers' convbn (models/psmnet/submodule.py:10-19, stackhourglass.py:22-62,73-98,135-149,
 // models/util_conv.py:150-179).
@@ -15,6 +17,7 @@ namespace {
 #include "conv_zs.hpp"
 #include "deconv_zs.hpp"
 #include "basicblock2d.hpp"
+#include "conv_wide2d.hpp"
 }  // namespace
 
 int dsmk::run_zs_f16(int pm, const ZsParams& p, int grid, hipStream_t s) {
@@ -33,5 +36,11 @@ int dsmk::run_split_f16(const Plan& pl, const ConvParams& p, hipStream_t s) {
 int dsmk::run_basicblock_f16(int pm, const BbParams& p, hipStream_t s) {
   if (pm == 2) return p.C == 64 ? launch_basicblock2d<2, 64>(p, s) : launch_basicblock2d<2, 32>(p, s);
   if (pm == 1) return p.C == 64 ? launch_basicblock2d<1, 64>(p, s) : launch_basicblock2d<1, 32>(p, s);
+  return DSM_ERR_UNSUPPORTED;
+}
+
+int dsmk::run_wide2d_f16(int pm, const WideParams& p, int grid, hipStream_t s) {
+  if (pm == 2) return launch_conv_wide2d<2>(p, grid, s);
+  if (pm == 1) return launch_conv_wide2d<1>(p, grid, s);
   return DSM_ERR_UNSUPPORTED;
 }

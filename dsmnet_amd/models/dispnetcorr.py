@@ -1,7 +1,10 @@
 """DispNetC on the MI355X cost-volume path: same names, attribute tree and return convention
-as models/dispnetcorr.py; `self.corr` is the HIP Corr1d (D=41), everything else is the
-reference's 2-D encoder/decoder; each decoder level's bias + ReLU + upsampling + myCat2d is one
-HIP launch in eval mode (`costvolume.decoder_level`, csrc/decoder.hip)."""
+as models/dispnetcorr.py; `self.corr` is the HIP Corr1d (D=41); the encoder's seven 3x3 layers of
+256 / 512 / 1024 channels (conv3b .. conv6b) run on the wide MFMA kernel in eval mode when the
+`costvolume` option `wide_conv2d` is on (csrc/conv_wide2d.hpp, `util_conv.Conv2dReLU`); each decoder
+level's bias + ReLU + upsampling + myCat2d is one HIP launch in eval mode (`costvolume.decoder_level`,
+csrc/decoder.hip); the stems, conv3a, the iconv / deconv layers and the heads are the reference's stock
+2-D layers."""
 import torch
 import torch.nn as nn
 
@@ -60,6 +63,8 @@ class dispnetcorr(nn.Module):
             x = getattr(self, name)(x)
             if name.endswith("b"):
                 skips[int(name[4])] = x             # conv3b, conv4b, conv5b
+        # the wide layers hand NHWC maps from one to the next (util_conv.Conv2dReLU); the chain is left once
+        x = x.contiguous()
         pr = self.pr6(x)
         out, out_scale = [pr], [6]
         for lvl in (5, 4, 3, 2, 1):

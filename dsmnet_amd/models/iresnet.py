@@ -1,7 +1,9 @@
 """iResNet on the MI355X cost-volume path: same names, attribute tree and return convention
 as models/iresnet.py.  Both correlations -- `corr` (D=81) and `r_corr` (kernel 3, stride 2,
-D=41, the only strided/box-filtered use in the reference) -- are the HIP Corr1d; the 2-D
-encoder/decoder/refinement layers are stock torch (outside the hot path)."""
+D=41, the only strided/box-filtered use in the reference) -- are the HIP Corr1d; the encoder's
+seven 3x3 layers of 256 / 512 / 1024 channels (conv3_1 .. conv6_1) run on the wide MFMA kernel in
+eval mode when the `costvolume` option `wide_conv2d` is on (`util_conv.Conv2dReLU`); the other 2-D
+encoder/decoder/refinement layers are stock torch."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -103,6 +105,8 @@ class iresnet(nn.Module):
             x = getattr(self, name)(x)
             if name.endswith("_1"):
                 skips[int(name[4])] = x             # conv3_1, conv4_1, conv5_1
+        # the wide layers hand NHWC maps from one to the next (util_conv.Conv2dReLU); the chain is left once
+        x = x.contiguous()
         pr = self.pr6(x)
         out, out_scale, keep = [pr], [6], {}
         for lvl in (5, 4, 3, 2, 1, 0):

@@ -3,7 +3,10 @@ cost-volume path runs.
 
   Corr1d                      -> HIP correlation kernel (util_conv.py:56-86)
   conv3d_bn / deconv3d_bn     -> blocks3d.ConvBN3d, one launch (util_conv.py:150-179)
-  conv2d_bn / deconv2d_bn / conv_res / net_init -- 2-D layers outside the hot path: stock
+  conv2d_bn(bn=False)         -> Conv2dReLU: Sequential(Conv2d, ReLU) whose wide 3x3 layers (256 / 512 /
+      1024 outputs: the DispNetC / iResNet encoders) run on the wide MFMA kernel in eval mode
+      (csrc/conv_wide2d.hpp; ``costvolume`` option ``wide_conv2d``)
+  deconv2d_bn / conv_res / net_init -- 2-D layers outside the hot path: stock
       torch modules in the same Sequential layout (state-dict keys match the reference).
 """
 import math
@@ -44,9 +47,44 @@ class Corr1d(nn.Module):
         return "kernel_size=%d, stride=%d, D=%d" % (self.kernel_size, self.stride, self.D)
 
 
+class Conv2dReLU(nn.Sequential):
+    """``Sequential(Conv2d, activation)`` of ``conv2d_bn(..., bn=False)`` (util_conv.py:100-117) with the
+    reference's child indices.  Eval mode, no autograd, fp32 on the GPU, the option ``wide_conv2d`` on,
+    an fp16 precision mode and a layer ``blocks2d.fused_ok`` admits with 256 / 512 / 1024 outputs:
+    convolution + bias + ReLU as one op on the wide MFMA kernel (NHWC in and out, the output carries
+    its absolute maximum for the next layer).  Everything else -- training, CPU tensors, k 5 / 7, odd
+    Cin, the narrower layers -- runs the two children as before."""
+
+    def __init__(self, conv, act):
+        super(Conv2dReLU, self).__init__(conv, act)
+        self._folded = None
+
+    def forward(self, x):
+        conv = self[0]
+        if (not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and
+                conv.out_channels in cv.WIDE2D_COUT and cv.get_option("wide_conv2d") and cv.needs_amax() and
+                isinstance(self[1], nn.ReLU)):
+            from ..blocks2d import _Folded2d, fused_ok, run_conv2d
+            if fused_ok(conv, x):
+                if self._folded is None:
+                    self._folded = _Folded2d()
+                return run_conv2d(self._folded, conv, None, x, relu=True)
+        return super(Conv2dReLU, self).forward(x)
+
+    def __deepcopy__(self, memo):
+        import copy
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = None if k == "_folded" else copy.deepcopy(v, memo)   # the pack cache is per instance
+        return new
+
+
 def _wrap(conv, out_planes, bn, activefun, norm):
     if not bn and not activefun:
         return conv
+    if not bn and type(conv) is nn.Conv2d:
+        return Conv2dReLU(conv, activefun)
     layers = [conv]
     if bn:
         layers.append(norm(out_planes))

@@ -215,6 +215,12 @@ typedef struct dsm_conv3d_args {
    * (the z-sliding kernel, "conv3d_zs_..."): DSM_ERR_UNSUPPORTED otherwise.  x_amax: of the features. */
   int          vol_virtual;
   int          vol_mask_left;
+  /* (ABI v7, additive) Scratch of the kernels that split the contraction over workgroups -- the wide 2-D
+   * layers, "conv2d_wide_..." with a split count above 1: dsm_conv3d_workspace_bytes(args) bytes of device
+   * memory, 16-byte aligned, contents undefined before and after the call; NULL / 0 where that query
+   * returns 0.  Too small or missing: DSM_ERR_ARG, nothing launched. */
+  void*        workspace;
+  size_t       workspace_bytes;
 } dsm_conv3d_args;
 /* fp32 operands, fp32-accurate products and sums: three-term bf16 split (six bf16 MFMAs per
  * product) or, with DSM_CONV_FP32_MFMA, the fp32-input MFMA */
@@ -230,6 +236,7 @@ typedef struct dsm_conv3d_args {
 #define DSM_CONV_COUT1_CHUNKED  0x2      /* Cout = 1: the chunked kernel instead of the z-sliding one */
 #define DSM_CONV_NO_NSPLIT      0x4      /* 2-D bf16x3 layers: one workgroup per tile (no N-split)    */
 #define DSM_CONV_NO_ONCE        0x8      /* A/B: the chunk-pipelined single-kind kernels instead of the single-tile (2-D 64 -> 64) and two-kind (stride-2 3-D) forms */
+#define DSM_CONV_KSPLIT_SHIFT   8        /* bits 8..13: wide 2-D layers: force the number of K-ranges (1..63, clamped to [ceil(Cin / 128), Cin / 16]) */
 #define DSM_CONV_TM_SHIFT       4        /* bits 4..7: force the tile height 4*TM rows (TM = 1, 2, 4) */
 #define DSM_CONV_BLOCKS_SHIFT   16       /* bits 16..31: force the persistent grid size               */
 
@@ -273,6 +280,18 @@ typedef struct {
 int dsm_basicblock2d_fwd(const dsm_basicblock2d_args* a, dsm_stream_t stream);
 
 int dsm_conv3d_fwd(const dsm_conv3d_args* args, dsm_stream_t stream);
+
+/* (ABI v7, additive) Wide 2-D layers -- Conv2d(k3, pad 1, stride 1 | 2) to Cout = 256 | 512 | 1024 from
+ * Cin % 16 == 0 (kd = 1, k = 3, dil = 1, no residual, natural output size), the encoder of DispNetC / iResNet
+ * (models/dispnetcorr.py:37-45 conv3b .. conv6b, models/iresnet.py conv3_1 .. conv6_1: conv2d_bn with
+ * bn = False, models/util_conv.py) -- run on "conv2d_wide_<f16x2|f16>_mfma_kernel<S,N,KS=K,units>": precision
+ * DSM_PREC_F16X2 or DSM_PREC_F16 only (DSM_PREC_F32, or DSM_CONV_FP32_MFMA: DSM_ERR_UNSUPPORTED -- the caller
+ * keeps its own layer).  The contraction (9 Cin) is cut into K ranges of 16-channel chunks, one workgroup
+ * each per (pixel block, N = 64 | 32 output channels); K > 1: the partial sums meet in `workspace`
+ * ([K][B*Ho*Wo][Cout] floats) and a second launch adds them in index order (no float atomics: the
+ * result is bit-identical from run to run; different K differ in the low bits).  This query: the bytes
+ * `workspace` must hold for `args` (flags included); 0 when the layer needs none or is not such a layer. */
+size_t dsm_conv3d_workspace_bytes(const dsm_conv3d_args* args);
 
 /* Name of the kernel variant dsm_conv3d_fwd would launch for `args` (tile shape and
  * channel chunk are chosen per layer) -- written NUL-terminated into buf[len];
