@@ -69,10 +69,7 @@ def fused_ok(conv, x):
     cin = x.shape[1]
     if cin % 16 != 0 or cin < conv.in_channels:
         return False
-    # variants compiled in csrc/conv3d.hip (DSM_CASE2D)
-    key = (s[0], conv.out_channels // 32, k[0], d[0])
-    return key in {(1, 1, 3, 1), (1, 2, 3, 1), (1, 4, 3, 1), (1, 4, 3, 2), (2, 1, 3, 1),
-                   (2, 2, 3, 1), (1, 1, 1, 1), (1, 4, 1, 1), (2, 2, 1, 1)}
+    return cv.conv2d_variant(conv.out_channels, s[0], k[0], d[0])
 
 
 # wide layers profiles/wide2d.md measured slower than the stock layer: (Cin, Cout, stride)

@@ -1150,7 +1150,9 @@ def stage_images_nhwc16(left, right=None):
 # ----------------------------------------------------------------------------
 # the 2-D towers in training: convolution with explicit gradients, batch-statistics BN
 # ----------------------------------------------------------------------------
-# (stride, Cout/32, k, dilation) variants of the 2-D MFMA convolution compiled in csrc/conv3d.hip
+# (stride, Cout/32, k, dilation) of the 2-D layers dsm_conv3d_plan accepts in every precision mode (the variant
+# lists of csrc/conv_common.hpp: a split kernel and an fp32-input kernel each); ``blocks2d.fused_ok`` reads this
+# set and tests/test_conv_plans.py holds it against the plan
 _CONV2D_VARIANTS = {(1, 1, 3, 1), (1, 2, 3, 1), (1, 4, 3, 1), (1, 4, 3, 2), (2, 1, 3, 1),
                     (2, 2, 3, 1), (1, 1, 1, 1), (1, 4, 1, 1), (2, 2, 1, 1)}
 

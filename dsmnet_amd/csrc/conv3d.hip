@@ -1023,7 +1023,7 @@ bool wide2d_units(const dsm_conv3d_args* a, WideParams* w) {
   return true;
 }
 
-int make_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
+int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
   DSM_REQUIRE(a && a->x && a->w_packed && a->y, DSM_ERR_ARG);
   DSM_REQUIRE(a->B > 0 && a->Cin > 0 && a->Cout > 0, DSM_ERR_ARG);
   DSM_REQUIRE(a->Di > 0 && a->Hi > 0 && a->Wi > 0 && a->Do > 0 && a->Ho > 0 && a->Wo > 0,
@@ -1160,6 +1160,18 @@ fp32_kernels:
   if (NT >= 2 && tiles4 <= 64 && pl->TM == 1) { pl->nsplit = NT; pl->NT = 1; }
   return DSM_OK;
 }
+// The selection above, refused where it names a variant that is not compiled (conv_common.hpp): the plan
+// query, the workspace query and the launch all start here, so they return the same code.
+int make_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
+  const int rc = select_plan_f32(a, pl);
+  if (rc != DSM_OK) return rc;
+  if (pl->kind != 7 && pl->kind != 8) {                  // 32-bit buffer offsets (kinds 7 / 8 bound theirs above)
+    const int kd = a->kd ? a->kd : 3, k = a->k ? a->k : 3;
+    DSM_REQUIRE(4ul * a->B * a->Di * a->Hi * a->Wi * a->Cin < (1ul << 32) &&
+                4ul * a->Cin * a->Cout * kd * k * k < (1ul << 32), DSM_ERR_UNSUPPORTED);
+  }
+  return plan_compiled(*pl) ? DSM_OK : DSM_ERR_UNSUPPORTED;
+}
 // precision: the split kernels (kinds 5, 6) also exist on fp16 terms (conv_split.hpp); every other
 // kernel computes in fp32 whatever `precision` says
 int make_plan(const dsm_conv3d_args* a, Plan* pl) {
@@ -1293,13 +1305,9 @@ extern "C" int dsm_conv3d_fwd(const dsm_conv3d_args* a, dsm_stream_t stream) {
     if (pl.pm == 3) return launch_conv_zs<3>(z, p.force_blocks, (hipStream_t)stream);
     return dsmk::run_zs_f16(pl.pm, z, p.force_blocks, (hipStream_t)stream);
   }
-  {
-    const unsigned long xb = 4ul * a->B * a->Di * a->Hi * a->Wi * a->Cin;
-    const int kd_ = a->kd ? a->kd : 3, k_ = a->k ? a->k : 3;
-    const unsigned long wb = 4ul * a->Cin * a->Cout * kd_ * k_ * k_;
-    DSM_REQUIRE(xb < (1ul << 32) && wb < (1ul << 32), DSM_ERR_UNSUPPORTED);   // 32-bit buffer offsets
-    p.xbytes = (unsigned)xb; p.wbytes = (unsigned)wb;
-  }
+  // 32-bit buffer offsets: make_plan_f32 has refused extents of 4 GiB and more
+  p.xbytes = (unsigned)(4ul * a->B * a->Di * a->Hi * a->Wi * a->Cin);
+  p.wbytes = (unsigned)(4ul * a->Cin * a->Cout * (a->kd ? a->kd : 3) * (a->k ? a->k : 3) * (a->k ? a->k : 3));
   hipStream_t s = (hipStream_t)stream;
   dsm_clear_stale_error();
   if (pl.kind == 3) {
@@ -1346,27 +1354,21 @@ extern "C" int dsm_conv3d_fwd(const dsm_conv3d_args* a, dsm_stream_t stream) {
     hipLaunchKernelGGL(conv3d_cout1_kernel<8>, dim3(blocks), dim3(NTHREADS), lds, s, p, p.w);
     return dsm_launch_status();
   }
+  // the variant lists of conv_common.hpp, which make_plan has checked (plan_compiled)
 #define DSM_CASE2D(S_, NT_, TM_, K_, DIL_) \
   if (pl.kind == 0 && pl.KZ == 1 && pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.K == K_ && \
-      pl.DIL == DIL_) return run_conv<S_, NT_, TM_, 16, 1, K_, DIL_>(p, s)
-  DSM_CASE2D(1, 1, 1, 3, 1); DSM_CASE2D(1, 1, 2, 3, 1); DSM_CASE2D(1, 2, 1, 3, 1);
-  DSM_CASE2D(1, 4, 1, 3, 1); DSM_CASE2D(1, 4, 1, 3, 2);
-  DSM_CASE2D(2, 1, 1, 3, 1); DSM_CASE2D(2, 2, 1, 3, 1);
-  DSM_CASE2D(1, 1, 1, 1, 1); DSM_CASE2D(1, 4, 1, 1, 1); DSM_CASE2D(2, 2, 1, 1, 1);
+      pl.DIL == DIL_) return run_conv<S_, NT_, TM_, 16, 1, K_, DIL_>(p, s);
+  DSM_CONV2D_VARIANTS(DSM_CASE2D)
 #undef DSM_CASE2D
   if (pl.KZ == 1) return DSM_ERR_UNSUPPORTED;
-#define DSM_CASE(KIND, S_, NT_, TM_, CK_, CALL) \
-  if (pl.kind == KIND && pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.CK == CK_) return CALL
-  DSM_CASE(1, 2, 1, 1, 16, (run_deconv<1, 16>(p, s)));
-  DSM_CASE(1, 2, 2, 1, 16, (run_deconv<2, 16>(p, s)));
-  DSM_CASE(0, 1, 1, 2, 16, (run_conv<1, 1, 2, 16>(p, s)));
-  DSM_CASE(0, 1, 1, 1, 16, (run_conv<1, 1, 1, 16>(p, s, pl.nsplit)));
-  DSM_CASE(0, 1, 2, 2, 8, (run_conv<1, 2, 2, 8>(p, s)));
-  DSM_CASE(0, 1, 2, 1, 16, (run_conv<1, 2, 1, 16>(p, s)));
-  DSM_CASE(0, 1, 4, 1, 16, (run_conv<1, 4, 1, 16>(p, s)));
-  DSM_CASE(0, 2, 1, 1, 8, (run_conv<2, 1, 1, 8>(p, s, pl.nsplit)));
-  DSM_CASE(0, 2, 2, 1, 8, (run_conv<2, 2, 1, 8>(p, s)));
-  DSM_CASE(0, 2, 4, 1, 8, (run_conv<2, 4, 1, 8>(p, s)));
+#define DSM_CASE_DECONV(NT_, CK_) \
+  if (pl.kind == 1 && pl.NT == NT_ && pl.CK == CK_) return run_deconv<NT_, CK_>(p, s);
+  DSM_DECONV3D_VARIANTS(DSM_CASE_DECONV)
+#undef DSM_CASE_DECONV
+#define DSM_CASE(S_, NT_, TM_, CK_) \
+  if (pl.kind == 0 && pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.CK == CK_) \
+    return run_conv<S_, NT_, TM_, CK_>(p, s, pl.nsplit);
+  DSM_CONV3D_VARIANTS(DSM_CASE)
 #undef DSM_CASE
   return DSM_ERR_UNSUPPORTED;
 }

@@ -30,6 +30,64 @@ struct ConvParams {
 // zs (kind 6, fp16 modes): the z-sliding transposed convolution (deconv_zs.hpp) instead of deconv_split_kernel
 struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int pm = 3; int once = 0; int zs = 0; };
 
+// The compiled variants of the kernels that exist in several instantiations.  Each list is expanded twice:
+// into plan_compiled() below, which make_plan consults, and into the chain of launches of its kind
+// (dsm_conv3d_fwd for kinds 0 / 1, dispatch_split for kind 5) -- a plan that make_plan returns therefore
+// launches, and a variant missing here is DSM_ERR_UNSUPPORTED from the plan query and the launch alike.
+// kind 0, 2-D (KZ = 1; 16-channel chunks): (S, NT, TM, K, DIL)
+#define DSM_CONV2D_VARIANTS(X) \
+  X(1, 1, 1, 3, 1) X(1, 1, 2, 3, 1) X(1, 2, 1, 3, 1) X(1, 4, 1, 3, 1) X(1, 4, 1, 3, 2) \
+  X(2, 1, 1, 3, 1) X(2, 2, 1, 3, 1) X(1, 1, 1, 1, 1) X(1, 4, 1, 1, 1) X(2, 2, 1, 1, 1)
+// kind 0, 3-D: (S, NT, TM, CK); the N-split forms (nsplit > 1) are the NT = 1, TM = 1 variants
+#define DSM_CONV3D_VARIANTS(X) \
+  X(1, 1, 2, 16) X(1, 1, 1, 16) X(1, 2, 2, 8) X(1, 2, 1, 16) X(1, 4, 1, 16) X(2, 1, 1, 8) X(2, 2, 1, 8) X(2, 4, 1, 8)
+// kind 1: (NT, CK)
+#define DSM_DECONV3D_VARIANTS(X) X(1, 16) X(2, 16)
+// kind 5 at stride 1, every precision mode: (NT, TM, KZ, DIL, NSPLIT).  (Stride 2 is <NT=2,TM=1> alone; the
+// single-tile `once` form is <1, 2, 1, 1, 2> with 64 inputs in the fp16 modes.)
+#define DSM_SPLIT_VARIANTS(X) \
+  X(1, 4, 3, 1, 1) X(1, 2, 3, 1, 1) X(2, 2, 3, 1, 1) X(2, 1, 3, 1, 1) \
+  X(1, 4, 1, 1, 1) X(1, 2, 1, 1, 1) X(2, 2, 1, 1, 1) X(2, 1, 1, 1, 1) X(4, 2, 1, 1, 1) X(4, 2, 1, 2, 1) \
+  X(1, 2, 1, 1, 2) X(2, 2, 1, 1, 2) X(1, 1, 3, 1, 2) X(1, 1, 3, 1, 4)
+
+// Is the kernel variant that `pl` selects compiled?  (Kinds 2, 3, 4, 7, 8 are single kernels.)
+inline bool plan_compiled(const Plan& pl) {
+  switch (pl.kind) {
+    case 0:
+      if (pl.KZ == 1) {
+        if (pl.nsplit != 1 || pl.CK != 16) return false;
+#define DSM_X(S_, NT_, TM_, K_, DIL_) \
+        if (pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.K == K_ && pl.DIL == DIL_) return true;
+        DSM_CONV2D_VARIANTS(DSM_X)
+#undef DSM_X
+        return false;
+      }
+      if (pl.nsplit != 1 && !(pl.NT == 1 && pl.TM == 1)) return false;
+#define DSM_X(S_, NT_, TM_, CK_) if (pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.CK == CK_) return true;
+      DSM_CONV3D_VARIANTS(DSM_X)
+#undef DSM_X
+      return false;
+    case 1:
+#define DSM_X(NT_, CK_) if (pl.S == 2 && pl.NT == NT_ && pl.TM == 1 && pl.CK == CK_) return true;
+      DSM_DECONV3D_VARIANTS(DSM_X)
+#undef DSM_X
+      return false;
+    case 5:
+      // the stride-2, `once` and kind-6 forms are no list: these three lines and the head of dispatch_split
+      // (conv_split.hpp) are written by hand and must say the same (`once` is set from Cin == 64 only, which
+      // the launch checks again); the name table of tests/test_conv_plans.py holds both to the launch
+      if (pl.S == 2) return pl.NT == 2 && pl.TM == 1 && pl.KZ == 3 && pl.DIL == 1 && pl.nsplit == 1;
+      if (pl.once && !(pl.NT == 1 && pl.TM == 2 && pl.KZ == 1 && pl.DIL == 1 && pl.nsplit == 2)) return false;
+#define DSM_X(NT_, TM_, KZ_, DIL_, NSPLIT_) \
+      if (pl.NT == NT_ && pl.TM == TM_ && pl.KZ == KZ_ && pl.DIL == DIL_ && pl.nsplit == NSPLIT_) return true;
+      DSM_SPLIT_VARIANTS(DSM_X)
+#undef DSM_X
+      return false;
+    case 6: return pl.NT == 1 || pl.NT == 2;
+    default: return true;
+  }
+}
+
 #ifndef DSM_DECONV_ZS
 #define DSM_DECONV_ZS 1       // 0: plan kind 6 stays on deconv_split_kernel in the fp16 modes (A/B builds)
 #endif

@@ -1201,6 +1201,7 @@ int run_deconv_split(ConvParams p, hipStream_t s) {
 // plan kinds 5 (convolution) and 6 (transposed convolution) at precision mode PM
 template <int PM>
 int dispatch_split(const Plan& pl, const ConvParams& p, hipStream_t s) {
+  // hand-written up to the list below: keep in step with plan_compiled (conv_common.hpp, kinds 5 / 6)
   if (pl.kind == 6) return pl.NT == 1 ? run_deconv_split<PM, 1>(p, s) : run_deconv_split<PM, 2>(p, s);
   if (pl.kind != 5) return DSM_ERR_UNSUPPORTED;
   if (pl.S == 2) {
@@ -1214,22 +1215,12 @@ int dispatch_split(const Plan& pl, const ConvParams& p, hipStream_t s) {
       return DSM_ERR_UNSUPPORTED;
     }
   }
-  if (pl.nsplit == 2) {                         // 2-D layers of 64 / 128 channels in two workgroup columns
-    if (pl.KZ == 1 && pl.NT == 1 && pl.TM == 2 && pl.DIL == 1) return run_conv_split<PM, 1, 2, 1, 1, 1, 2>(p, s);
-    if (pl.KZ == 1 && pl.NT == 2 && pl.TM == 2 && pl.DIL == 1) return run_conv_split<PM, 2, 2, 1, 1, 1, 2>(p, s);
-    if (pl.KZ == 3 && pl.NT == 1 && pl.TM == 1) return run_conv_split<PM, 1, 1, 3, 1, 1, 2>(p, s);
-    return DSM_ERR_UNSUPPORTED;
-  }
-  if (pl.nsplit == 4) {                         // 3-D, 128 output channels on a small volume
-    if (pl.KZ == 3 && pl.NT == 1 && pl.TM == 1) return run_conv_split<PM, 1, 1, 3, 1, 1, 4>(p, s);
-    return DSM_ERR_UNSUPPORTED;
-  }
-#define DSM_CASE_SPLIT(NT_, TM_, KZ_, DIL_) \
-  if (pl.NT == NT_ && pl.TM == TM_ && pl.KZ == KZ_ && pl.DIL == DIL_) return run_conv_split<PM, NT_, TM_, KZ_, DIL_>(p, s)
-  DSM_CASE_SPLIT(1, 4, 3, 1); DSM_CASE_SPLIT(1, 2, 3, 1); DSM_CASE_SPLIT(2, 2, 3, 1); DSM_CASE_SPLIT(2, 1, 3, 1);
-  DSM_CASE_SPLIT(1, 4, 1, 1); DSM_CASE_SPLIT(1, 2, 1, 1); DSM_CASE_SPLIT(2, 2, 1, 1); DSM_CASE_SPLIT(2, 1, 1, 1);
-  DSM_CASE_SPLIT(4, 2, 1, 1);
-  DSM_CASE_SPLIT(4, 2, 1, 2);
+  // (NSPLIT = 2: 2-D layers of 64 / 128 channels, and the 64-channel 3-D layers on 4-row tiles, in two
+  // workgroup columns; NSPLIT = 4: 3-D, 128 output channels on a small volume)
+#define DSM_CASE_SPLIT(NT_, TM_, KZ_, DIL_, NSPLIT_) \
+  if (pl.NT == NT_ && pl.TM == TM_ && pl.KZ == KZ_ && pl.DIL == DIL_ && pl.nsplit == NSPLIT_) \
+    return run_conv_split<PM, NT_, TM_, KZ_, DIL_, 1, NSPLIT_>(p, s);
+  DSM_SPLIT_VARIANTS(DSM_CASE_SPLIT)
 #undef DSM_CASE_SPLIT
   return DSM_ERR_UNSUPPORTED;
 }

@@ -295,7 +295,13 @@ size_t dsm_conv3d_workspace_bytes(const dsm_conv3d_args* args);
 
 /* Name of the kernel variant dsm_conv3d_fwd would launch for `args` (tile shape and
  * channel chunk are chosen per layer) -- written NUL-terminated into buf[len];
- * used by bench.py to attribute per-launch timings.  No launch, no device access. */
+ * used by bench.py to attribute per-launch timings.  No launch, no device access.
+ * Returns the SAME error codes the launch would return for `args` (as the corr1d, soft-argmin and volume
+ * queries do): the plan, dsm_conv3d_workspace_bytes and dsm_conv3d_fwd share one selection, and a variant
+ * that is not compiled (say Conv2d(k3, dilation 2) to 32 or 64 channels on the split kernels) is
+ * DSM_ERR_UNSUPPORTED here, with buf = "", not a name.  The launch's alone: a missing or short `workspace`
+ * of the wide layers (DSM_ERR_ARG), DSM_ERR_LAUNCH from the runtime, and the launchers' own tile-count bounds,
+ * which no extent under the plan's 4 GiB bound reaches. */
 int dsm_conv3d_plan(const dsm_conv3d_args* args, char* buf, int len);
 
 /* ---------------------------------------------------------------------------
