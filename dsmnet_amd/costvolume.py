@@ -530,27 +530,65 @@ def get_option(name):
 # on the tensor object as ``_dsm_amax``; a tensor without one (an input of the model, the result of
 # a stock torch op) gets it from one ``dsm_absmax`` pass.  Slots come from a per-device arena that a
 # model forward zeroes once (``amax_scope``), so that a forward costs one fill, not one per layer.
+#
+# A slot outlives the launch that wrote it only as long as its arena is not begun again: every
+# ``begin`` zeroes the buffer and hands the same addresses out anew, while tensors of the earlier
+# scope (an input saved for backward, an output the caller kept) still carry their slot.  Each slot
+# therefore remembers the generation of the arena it was cut from, and ``amax_of`` serves it only
+# while that is still the arena's generation; a stale one is replaced by a fresh ``dsm_absmax`` pass
+# over the tensor.  All of it is host book-keeping: no device value is read, a captured ``begin``
+# stays one memset inside the graph, and a slot that is valid costs nothing extra.  (DESIGN.md
+# section 9, "state that outlives a launch")
 class _AmaxArena(object):
+    """``depth``, ``used`` and ``generation`` are per device: a scope opened for one device neither
+    continues nor skips the ``begin`` of another's.  Process-wide on purpose, not thread-local: the
+    backward of a step runs on autograd's device thread and must see the scope its forward opened."""
     SLOTS = 2048
 
     def __init__(self):
-        self.buf, self.used, self.depth = {}, {}, 0
+        self.buf, self.used, self.depth, self.generation = {}, {}, {}, {}
+
+    @staticmethod
+    def key(device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:          # "cuda" is the current device
+            return (device.type, torch.cuda.current_device())
+        return (device.type, device.index)
 
     def begin(self, device):
-        key = (device.type, device.index)
+        key = self.key(device)
         if key not in self.buf:
             self.buf[key] = torch.zeros(self.SLOTS, device=device, dtype=torch.float32)
         else:
             self.buf[key].zero_()
         self.used[key] = 0
+        self.generation[key] = self.generation.get(key, 0) + 1      # every slot handed out before is stale
+
+    def enter(self, device):
+        key = self.key(device)
+        if self.depth.get(key, 0) == 0:
+            self.begin(device)
+        self.depth[key] = self.depth.get(key, 0) + 1
+
+    def leave(self, device):
+        self.depth[self.key(device)] -= 1
 
     def slot(self, device):
-        key = (device.type, device.index)
-        if self.depth > 0 and key in self.buf and self.used[key] < self.SLOTS:
+        """A zeroed float for one launch to write a maximum into: the next slot of the open scope's
+        arena, or -- outside any scope, or past ``SLOTS`` -- a private scalar that nothing invalidates."""
+        key = self.key(device)
+        if self.depth.get(key, 0) > 0 and self.used[key] < self.SLOTS:
             i = self.used[key]
             self.used[key] = i + 1
-            return self.buf[key][i:i + 1]
+            s = self.buf[key][i:i + 1]
+            s._dsm_generation = (key, self.generation[key])
+            return s
         return torch.zeros(1, device=device, dtype=torch.float32)
+
+    def valid(self, slot):
+        """Does ``slot`` still hold what its producer wrote (its arena has not been begun again)?"""
+        tag = getattr(slot, "_dsm_generation", None)
+        return tag is None or self.generation.get(tag[0]) == tag[1]
 
 
 _ARENA = _AmaxArena()
@@ -558,17 +596,17 @@ _ARENA = _AmaxArena()
 
 class amax_scope(object):
     """``with amax_scope(device):`` around a model forward: the absolute-maximum slots of every
-    launch inside come from one arena, zeroed once on entry (nested scopes share the outer one).
-    A no-op unless an fp16 precision is selected."""
+    launch inside come from one arena, zeroed once on entry (nested scopes share the outer one, and
+    leaving the inner one changes nothing).  Entering an outermost scope ends the validity of every
+    slot the device's arena handed out before: ``amax_of`` recomputes those.  A no-op unless an fp16
+    precision is selected."""
 
     def __init__(self, device):
         self.device = device
 
     def __enter__(self):
         if needs_amax():
-            if _ARENA.depth == 0:
-                _ARENA.begin(self.device)
-            _ARENA.depth += 1
+            _ARENA.enter(self.device)
             self.entered = True
         else:
             self.entered = False
@@ -576,7 +614,7 @@ class amax_scope(object):
 
     def __exit__(self, *exc):
         if self.entered:
-            _ARENA.depth -= 1
+            _ARENA.leave(self.device)
         return False
 
 
@@ -585,10 +623,28 @@ def needs_amax():
 
 
 def absmax(x):
-    """Device scalar holding max |x| (one pass, ``dsm_absmax``), also remembered on ``x``."""
+    """Device scalar holding exactly ``x.abs().max()`` (``dsm_absmax``), also remembered on ``x``.
+
+    ``dsm_absmax`` scans ``numel()`` floats from a 16-byte-aligned address, so:
+      * a dtype other than float32 raises ``TypeError`` before any launch;
+      * a tensor that does not own a dense block of memory (a channel or spatial slice, an expanded
+        tensor) is reduced over ``x.contiguous()``: one copy, the exact maximum of the elements of
+        ``x`` and of nothing else;
+      * a dense view at a storage offset that is not 16-byte aligned is reduced over a copy too.
+    A dense tensor in any dimension order (channels_last included) is scanned in place.  An empty
+    tensor raises ``ValueError``.  ``amax_of`` inherits all of this."""
+    if x.dtype != torch.float32:
+        raise TypeError("absmax: float32 only, got %s" % (x.dtype,))
+    if x.numel() == 0:
+        raise ValueError("absmax of an empty tensor")
+    src = x.detach()
+    if not _dense(src):
+        src = src.contiguous()
+    if src.data_ptr() % 16:
+        src = src.clone(memory_format=torch.contiguous_format)
     slot = _ARENA.slot(x.device)
     with torch.cuda.device(x.device), _timed("absmax_kernel", 4.0 * x.numel()):
-        rc = _lib.load().dsm_absmax(_p(x), x.numel(), _p(slot), _stream())
+        rc = _lib.load().dsm_absmax(_p(src), src.numel(), _p(slot), _stream())
     _lib.check(rc, "dsm_absmax")
     try:
         x._dsm_amax = slot
@@ -597,15 +653,29 @@ def absmax(x):
     return slot
 
 
+def _dense(x):
+    """Do the elements of ``x`` fill one block of ``numel()`` elements, each address once (any order)?"""
+    if x.is_contiguous():
+        return True
+    expect = 1
+    for size, stride in sorted(((n, s) for n, s in zip(x.shape, x.stride()) if n != 1), key=lambda t: t[1]):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
 def amax_of(x):
-    """The absolute-maximum scalar of ``x``: the one its producer attached, else a fresh pass."""
+    """The absolute-maximum scalar of ``x``: the one its producer attached, while the arena it was cut
+    from has not been begun again (``amax_scope``); else a fresh pass (``absmax``)."""
     slot = getattr(x, "_dsm_amax", None)
-    return slot if slot is not None else absmax(x)
+    return slot if slot is not None and _ARENA.valid(slot) else absmax(x)
 
 
 def carry_amax(dst, *srcs):
     """``dst`` holds values bounded by the maximum over ``srcs`` (a view, a slice, a concatenation):
-    hand the bound on without a pass when a single source carries one."""
+    hand the bound on without a pass when a single source carries one.  The slot object itself is
+    handed on, and its validity with it: the bound of ``dst`` goes stale when its source's does."""
     slots = [getattr(t, "_dsm_amax", None) for t in srcs]
     if len(slots) == 1 and slots[0] is not None:
         dst._dsm_amax = slots[0]

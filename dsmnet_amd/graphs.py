@@ -71,7 +71,12 @@ class GraphedTrainStep(object):
     A rank whose batch has no ground-truth pixel contributes zero gradients and takes part in the
     collective all the same; the number of ranks that had ground truth rides in the same buffer
     and the optimizer step is skipped on every rank together when it is zero (as
-    ``train.train_step`` does).
+    ``train.train_step`` does).  ``model.zero_grad()`` / ``optim.zero_grad()`` between steps are
+    harmless in this form: the views are re-attached before the eager optimizer step.
+
+    Every call drops the cached packed weights and BN folds of the eval path
+    (``blocks3d.invalidate_folded_caches``): a replay changes weights and running statistics without
+    running the Python that would have bumped their version counters.
 
     An eager backward through the same model before the capture leaves gradient tensors and
     autograd buffers that were allocated OUTSIDE the capture's private pool, on the default
@@ -156,6 +161,7 @@ class GraphedTrainStep(object):
 
     def _exchange_and_update(self):
         """The part of a multi-rank step that stays outside the graph."""
+        self.flatgrads.reattach()                # a zero_grad() since the last step unbound the views
         n_gt = self.flatgrads.allreduce(self.world)
         if float(n_gt) > 0:                      # (a host read: one scalar per step)
             self.optim.step()
@@ -164,8 +170,13 @@ class GraphedTrainStep(object):
         if batch.shape[0] != self.batch.shape[0] or batch.shape[2:] != self.batch.shape[2:]:
             raise ValueError("GraphedTrainStep was captured for %s, got %s"
                              % (tuple(self.batch.shape), tuple(batch.shape)))
+        from . import blocks3d
         self.batch.copy_(batch[:, :7])
         self.graph.replay()
+        # the replay ran no Python: the captured optimizer step and the BN kernels' raw-pointer writes
+        # bumped no version counter, so every fold made from these tensors is stale (DESIGN.md
+        # section 9, "state that outlives a launch")
+        blocks3d.invalidate_folded_caches()
         if self.flatgrads is not None:
             self._exchange_and_update()
         return self.loss, self.disps

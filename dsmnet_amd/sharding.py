@@ -136,6 +136,23 @@ class FlatGradients(object):
             p.grad = self.flat[off: off + n].view_as(p)
             off += n
 
+    def reattach(self):
+        """Rebind every ``p.grad`` that is no longer this parameter's view of the flat buffer -- after
+        ``zero_grad()`` at torch's default (``set_to_none=True``), or after somebody assigned a
+        gradient of their own.  Whoever writes gradients to the buffer's fixed addresses (a captured
+        backward) calls this before an eager ``optim.step()``, which otherwise sees no gradient and
+        updates nothing.  Host book-keeping only; returns the number of parameters rebound."""
+        off, rebound = 0, 0
+        base, item = self.flat.data_ptr(), self.flat.element_size()
+        for p in self.params:
+            n = p.numel()
+            g = p.grad
+            if g is None or g.data_ptr() != base + off * item or g.shape != p.shape or not g.is_contiguous():
+                p.grad = self.flat[off: off + n].view_as(p)
+                rebound += 1
+            off += n
+        return rebound
+
     @property
     def extra(self):
         return self.flat[self.total:]

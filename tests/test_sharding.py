@@ -80,6 +80,49 @@ def test_world_size_2_gloo():
     assert all(r[1] and r[2] for r in results), results
 
 
+def test_flat_gradients_are_rebound_after_zero_grad():
+    """``model.zero_grad()`` / ``optim.zero_grad()`` at torch's default set every ``p.grad`` to None, while a
+    captured backward keeps writing to the flat buffer's fixed addresses: ``reattach`` -- what
+    ``GraphedTrainStep.__call__`` runs before the eager ``optim.step()`` -- puts every view back at its offset."""
+    from dsmnet_amd import graphs
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(3, 5), torch.nn.Linear(5, 2, bias=False), torch.nn.Linear(2, 7))
+    model[1].weight.requires_grad_(False)             # not part of the buffer: offsets skip it
+    opt = torch.optim.SGD(model.parameters(), lr=0.5)
+    fg = sharding.FlatGradients(model.parameters(), n_extra=1)
+    params = [p for p in model.parameters() if p.requires_grad]
+    assert fg.flat.numel() == sum(p.numel() for p in params) + 1
+
+    def bound():
+        off = 0
+        for p in params:
+            assert p.grad is not None and p.grad.shape == p.shape and p.grad.is_contiguous()
+            assert p.grad.data_ptr() == fg.flat.data_ptr() + 4 * off, off
+            off += p.numel()
+        assert model[1].weight.grad is None
+    bound()
+    assert fg.reattach() == 0                         # bound already: nothing is touched
+    views = [p.grad for p in params]
+    assert fg.reattach() == 0 and all(p.grad is v for p, v in zip(params, views))
+    for zero in (model.zero_grad, opt.zero_grad):
+        zero()                                        # torch's default: set_to_none=True
+        assert all(p.grad is None for p in params)
+        assert fg.reattach() == len(params)
+        bound()
+    params[1].grad = torch.ones_like(params[1])       # a gradient somebody assigned: not the buffer's
+    assert fg.reattach() == 1
+    bound()
+    # the multi-rank step's own host part (called on a stand-in: no graph, no GPU): a captured backward
+    # has left 2.0 everywhere in the buffer after a zero_grad(); the optimizer must apply exactly that
+    from types import SimpleNamespace
+    model.zero_grad()
+    fg.flat.fill_(2.0)                                # the trailing float too: "one rank had ground truth"
+    before = [p.detach().clone() for p in params]
+    graphs.GraphedTrainStep._exchange_and_update(SimpleNamespace(flatgrads=fg, world=1, optim=opt))
+    bound()
+    assert all(torch.equal(p.detach(), b - 1.0) for p, b in zip(params, before))
+
+
 class _ToyStereo(torch.nn.Module):
     """A stock-torch stand-in with the models' call contract: (imL, imR) -> (scales, disps)."""
 
