@@ -111,6 +111,7 @@ SIGNATURES = {
     "dsm_conv3d_workspace_bytes": (c_size_t, [ctypes.POINTER(Conv3dArgs)]),
     "dsm_conv3d_wgrad": (c_int, [c_void_p] * 4 + [c_int] * 12 + [c_void_p] * 3),
     "dsm_conv2d_wgrad": (c_int, [c_void_p] * 4 + [c_int] * 11 + [c_void_p] * 3),
+    "dsm_bias_relu_bwd": (c_int, [c_void_p] * 6 + [ctypes.c_long, c_int, c_void_p]),
     "dsm_conv3d_cout1_bwd": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
     "dsm_deconv3d_cout1_bwd": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
     "dsm_bn3d_train_fwd": (c_int, [ctypes.POINTER(Bn3dArgs), c_void_p]),

@@ -92,6 +92,30 @@ def _wide_ok(conv, x):
     return 4 * B * cin * H * W < 2 ** 31 and B * Ho * Wo * conv.out_channels < 2 ** 31 - 1
 
 
+def wide_train_ok(conv, act, x):
+    """Does ``Sequential(conv, act)`` train on ``costvolume.wide_conv2d_relu`` for the fp32 CUDA map ``x``?
+    The option ``wide_conv2d_train``, an fp16 precision mode, nn.ReLU, k3 / dilation 1 / pad 1 / stride 1 or 2
+    with a bias, Cin AND Cout in 256 / 512 / 1024 (so that backward-data, a wide layer of Cin outputs, and the
+    weight gradient both have a kernel), the size limits of the forward (``_wide_ok``) and those of the
+    backward-data launch, whose output is ``x`` and whose input is the layer's output gradient."""
+    if not (cv.get_option("wide_conv2d_train") and isinstance(act, nn.ReLU) and isinstance(conv, nn.Conv2d) and
+            x.is_cuda and x.dtype == torch.float32):
+        return False
+    k, s, d, p = conv.kernel_size, conv.stride, conv.dilation, conv.padding
+    if k != (3, 3) or s[0] != s[1] or s[0] not in (1, 2) or d != (1, 1) or p != (1, 1) or conv.groups != 1:
+        return False
+    if conv.bias is None or conv.padding_mode != "zeros" or conv.weight.dtype != torch.float32:
+        return False
+    if conv.in_channels not in cv.WIDE2D_COUT or conv.out_channels not in cv.WIDE2D_COUT:
+        return False
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // s[0] + 1, (W - 1) // s[0] + 1
+    # the backward-data launch: stride-1 geometry over x, 32-bit offsets into the output gradient it reads
+    if W > 2032 or B * H * W >= 2 ** 20 or 4 * B * Ho * Wo * conv.out_channels >= 2 ** 31:
+        return False
+    return _wide_ok(conv, x)
+
+
 class _Folded2d(object):
     def __init__(self):
         self.key = None

@@ -442,6 +442,7 @@ def conv3d_plan_name(args):
 # host-side options, absolute maxima of the fp16 precisions, the virtual cost volume
 # ----------------------------------------------------------------------------
 import os as _os
+import weakref
 
 # host-side options (the library itself reads no environment variable): "conv_precision" starts from
 # DSM_CONV_PRECISION=bf16x3|fp32|f16x2|f16 so that scripts and the parity tests can switch whole runs
@@ -469,7 +470,8 @@ _WIDE_CONV2D_DEFAULT = False
 _OPTIONS = {"fuse_volume": True, "fuse_blocks": True, "conv_precision": _env_precision(), "conv_flags": 0,
             "separable_volume": _env_flag("DSM_SEPARABLE_VOLUME", True), "separable_flags": 0,
             "fused_supervised_loss": _env_flag("DSM_FUSED_SUP_LOSS", True),
-            "wide_conv2d": _env_flag("DSM_WIDE_CONV2D", _WIDE_CONV2D_DEFAULT)}
+            "wide_conv2d": _env_flag("DSM_WIDE_CONV2D", _WIDE_CONV2D_DEFAULT),
+            "wide_conv2d_train": _env_flag("DSM_WIDE_CONV2D_TRAIN", False)}
 
 
 def set_option(name, value):
@@ -492,6 +494,10 @@ def set_option(name, value):
     ``wide_conv2d`` -- the 256 / 512 / 1024-channel 3x3 layers of the DispNetC / iResNet encoders run on the
     wide MFMA kernel (csrc/conv_wide2d.hpp; eval, fp16 modes) instead of the stock layer; starts from
     DSM_WIDE_CONV2D=0|1;
+    ``wide_conv2d_train`` -- the same layers with Cin and Cout both in 256 / 512 / 1024 train on
+    ``wide_conv2d_relu`` under autograd (forward, ReLU + bias backward, backward-data and weight gradient on
+    this project's kernels; fp16 modes), whatever ``wide_conv2d`` says; default off (profiles/wide2d_train.md),
+    starts from DSM_WIDE_CONV2D_TRAIN=0|1;
     ``conv_flags`` -- raw dsm_conv3d_args.flags bits (tile height, grid size, K-ranges of the wide layers)."""
     if name == "conv_fp32":
         old = _OPTIONS["conv_precision"] == "fp32"
@@ -690,8 +696,8 @@ def _split_kernel_layer(a):
     5 / 6)?  3x3(x3) taps, Cin % 16 == 0, Cout a multiple of 32 up to 64 (3-D; 128 on small volumes at
     stride 1) / 128 (2-D); stride 1, 3-D stride 2 to 64 channels, or transposed from Cin % 32 == 0."""
     kd, k = (a.kd or 3), (a.k or 3)
-    if kd == 1 and k == 3 and a.Cin % 16 == 0 and a.Cout in WIDE2D_COUT:       # conv_wide2d.hpp (plan kind 8)
-        return not a.transposed and (a.dil or 1) == 1
+    if kd == 1 and k == 3 and a.Cin % 16 == 0 and a.Cout in WIDE2D_COUT:       # conv_wide2d.hpp (plan kinds 8, 9)
+        return (a.dil or 1) == 1 and (not a.transposed or a.stride == 2)
     if k != 3 or a.Cin % 16 or a.Cout % 32 or a.Cout > 128:
         return False
     if kd == 3 and a.Cout == 128:                    # four workgroup columns of 32: small volumes, stride 1 only
@@ -884,6 +890,69 @@ def conv2d_block(x, packed_weight, cout, scale=None, shift=None, residual=None, 
     _lib.check(rc, "dsm_conv3d_fwd")
     del keep, ws
     return y
+
+
+def conv2d_transposed_block(x, packed_weight, cout, out_size):
+    """Backward-data of a stride-2 wide layer (plan kind 9 of ``dsm_conv3d_fwd``, the transposed mode of the
+    wide kernel): ``conv_transpose2d(x, W, stride 2, padding 1, output_padding 1)[:, :, :Ho, :Wo]`` with
+    ``packed_weight`` the pack of the flipped, in/out-transposed ``W`` and ``out_size`` = (Ho, Wo), the extent
+    of the tensor whose gradient this is (2 Hi - 1 <= Ho <= 2 Hi).  ``x``: (B, Cin, Hi, Wi) channels_last,
+    Cin % 16 == 0; ``cout`` in 256 / 512 / 1024; fp16 precision modes only."""
+    _require_device("conv2d_transposed_block", x, packed_weight)
+    if not x.is_contiguous(memory_format=_CL2D):
+        x = carry_amax(x.contiguous(memory_format=_CL2D), x)
+    B, cin, Hi, Wi = x.shape
+    Ho, Wo = int(out_size[0]), int(out_size[1])
+    if not (2 * Hi - 1 <= Ho <= 2 * Hi and 2 * Wi - 1 <= Wo <= 2 * Wi):
+        raise ValueError("conv2d_transposed_block: output %s is no stride-2 source of %s"
+                         % ((Ho, Wo), (Hi, Wi)))
+    dev = packed_weight.device
+    y = torch.empty((B, cout, Ho, Wo), device=dev, dtype=torch.float32, memory_format=_CL2D)
+    a = _lib.Conv3dArgs()
+    a.x, a.w_packed, a.y = x.data_ptr(), packed_weight.data_ptr(), y.data_ptr()
+    a.B, a.Cin, a.Cout = B, cin, cout
+    a.Di, a.Hi, a.Wi = 1, Hi, Wi
+    a.Do, a.Ho, a.Wo = 1, Ho, Wo
+    a.stride, a.transposed, a.relu = 2, 1, 0
+    a.kd, a.k, a.dil = 1, 3, 1
+    a.flags = _conv_flags()
+    keep = _set_precision(a, x, y)
+    ws = None
+    nws = _lib.load().dsm_conv3d_workspace_bytes(ctypes.byref(a))
+    if nws:                                          # K-split partial sums, from torch's caching allocator
+        ws = torch.empty(nws // 4, device=dev, dtype=torch.float32)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nws
+    with torch.cuda.device(dev), _timed(lambda: conv3d_plan_name(a), 18.0 * cin * cout * B * Ho * Wo):
+        rc = _lib.load().dsm_conv3d_fwd(ctypes.byref(a), _stream())
+    _lib.check(rc, "dsm_conv3d_fwd")
+    del keep, ws
+    return y
+
+
+def bias_relu_bwd(gy, y, need_db=True):
+    """``g = where(y > 0, gy, 0)`` as a tensor of its own (``gy`` is never written), ``db = g.sum over pixels``
+    in a fixed order (or None) and, in the fp16 modes, the maximum of ``|g|`` attached to ``g`` -- one pass,
+    ``dsm_bias_relu_bwd`` (csrc/relu_bwd.hip).  ``gy``, ``y``: (B, C, H, W) channels_last, C % 4 == 0."""
+    _require_device("bias_relu_bwd", gy, y)
+    _same_shape("bias_relu_bwd", gy, y)
+    if not gy.is_contiguous(memory_format=_CL2D):
+        gy = gy.contiguous(memory_format=_CL2D)
+    if not y.is_contiguous(memory_format=_CL2D):
+        y = y.contiguous(memory_format=_CL2D)
+    B, C, H, W = y.shape
+    M = B * H * W
+    g = torch.empty((B, C, H, W), device=y.device, dtype=torch.float32, memory_format=_CL2D)
+    db = ws = ga = None
+    if need_db:
+        db = torch.empty(C, device=y.device, dtype=torch.float32)
+        ws = torch.empty(min(512, (M + 7) // 8) * C, device=y.device, dtype=torch.float32)
+    if needs_amax():
+        ga = _ARENA.slot(y.device)
+        g._dsm_amax = ga
+    with torch.cuda.device(y.device), _timed("dsm_bias_relu_bwd", 0.0):
+        rc = _lib.load().dsm_bias_relu_bwd(_p(gy), _p(y), _p(g), _p(db), _p(ws), _p(ga), M, C, _stream())
+    _lib.check(rc, "dsm_bias_relu_bwd")
+    return g, db
 
 
 def basicblock2d_ok(x, cin, cout, stride, dilation):
@@ -1231,14 +1300,14 @@ def conv2d_variant(cout, stride, k, dilation):
     return cout in (32, 64, 128) and (stride, cout // 32, k, dilation) in _CONV2D_VARIANTS
 
 
-def _wgrad2d(x_cl, g_cl, stride, dilation):
+def _wgrad2d(x_cl, g_cl, stride, dilation, label="conv2d_wgrad_kernel"):
     """dW[g][c][ky][kx] = sum_v X[v*stride + (k - 1)*dilation][c] G[v][g]  ->  (cg, cx, 3, 3)."""
     B, cx, Hx, Wx = x_cl.shape
     _, cg, Hg, Wg = g_cl.shape
     ws = torch.empty((cx // 32) * (cg // 32) * 9 * 1024, device=x_cl.device, dtype=torch.float32)
     dw = torch.empty((cg, cx, 3, 3), device=x_cl.device, dtype=torch.float32)
     prec, xa, ga = _wgrad_precision(x_cl, g_cl)
-    with torch.cuda.device(x_cl.device), _timed("conv2d_wgrad_kernel", 18.0 * cx * cg * B * Hg * Wg):
+    with torch.cuda.device(x_cl.device), _timed(label, 18.0 * cx * cg * B * Hg * Wg):
         rc = _lib.load().dsm_conv2d_wgrad(_p(x_cl), _p(g_cl), _p(ws), _p(dw), B, cx, cg, Hx, Wx,
                                           Hg, Wg, int(stride), int(dilation), _conv_flags(), prec,
                                           _p(xa), _p(ga), _stream())
@@ -1301,6 +1370,106 @@ class Conv2dFunction(torch.autograd.Function):
 
 def conv2d(x, weight, stride=1, dilation=1):
     return Conv2dFunction.apply(x, weight, int(stride), int(dilation))
+
+
+# ----------------------------------------------------------------------------
+# training through the wide 3x3 layers (DispNetC conv3b .. conv6b, iResNet conv3_1 .. conv6_1)
+# ----------------------------------------------------------------------------
+# Forward and gradient packs of a wide layer's weight, made once per weight version: DispNetC's forward runs
+# twice per self-supervised step on the same weights, and both backwards need the flipped / transposed
+# pack.  Keyed like blocks2d._Folded2d (storage address, ``_version``, the epoch that a hipGraph replay
+# advances); an entry is replaced when its weight changes and dropped with the weight.
+_WIDE_PACKS = {}
+_WIDE_PACK_MISSES = {"forward": 0, "gradient": 0}      # packs made so far (tests count them)
+
+
+def _wide_pack_entry(weight):
+    from .blocks3d import _versions                    # (blocks3d imports this module)
+    key = _versions(weight)
+    ent = _WIDE_PACKS.get(id(weight))
+    if ent is None or ent["ref"]() is not weight:
+        weakref.finalize(weight, _WIDE_PACKS.pop, id(weight), None)
+        ent = None
+    if ent is None or ent["key"] != key:
+        ent = {"ref": weakref.ref(weight), "key": key, "forward": None, "gradient": None}
+        _WIDE_PACKS[id(weight)] = ent
+    return ent
+
+
+def _wide_pack(ent, weight, which):
+    if ent[which] is None:
+        w = weight.detach()
+        if which == "gradient":                        # backward-data: a convolution with flipped W^T
+            w = w.flip(2, 3).transpose(0, 1).contiguous()
+        ent[which] = pack_conv2d_weight(w)
+        _WIDE_PACK_MISSES[which] += 1
+    return ent[which]
+
+
+class WideConv2dReLUFunction(torch.autograd.Function):
+    """y = relu(conv2d(x, weight, k3, pad 1, stride 1 | 2) + bias) for Cin and Cout in 256 / 512 / 1024, NHWC,
+    every pass on the gfx950 kernels (fp16 precision modes): the wide MFMA kernel forward;
+    ``dsm_bias_relu_bwd`` for the masked gradient, the bias gradient and the gradient's maximum;
+    backward-data on the wide kernel again (stride 1: flipped transposed weights; stride 2: its transposed
+    mode); ``dsm_conv2d_wgrad`` for the weight gradient.  No device value is read on the host and the
+    workspaces come from torch's allocator per call, so a step captures into a hipGraph.  The backward runs in
+    the precision mode of its forward, whatever ``conv_precision`` says by then.  In the reference
+    this is autograd through ``conv2d_bn(..., bn=False)`` (models/util_conv.py:100-117)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride):
+        _require_device("WideConv2dReLUFunction", x, weight, bias)
+        cout, cin, k, k2 = weight.shape
+        if k != 3 or k2 != 3 or cin not in WIDE2D_COUT or cout not in WIDE2D_COUT or stride not in (1, 2):
+            raise ValueError("wide_conv2d_relu: no kernels for weight %s at stride %s"
+                             % (tuple(weight.shape), stride))
+        if bias is None:
+            raise ValueError("wide_conv2d_relu: the layer has a bias")
+        if not x.is_contiguous(memory_format=_CL2D):
+            x = carry_amax(x.contiguous(memory_format=_CL2D), x)
+        ent = _wide_pack_entry(weight)
+        y = conv2d_block(x, _wide_pack(ent, weight, "forward"), cout, None, bias.detach().contiguous(),
+                         stride=stride, relu=1)
+        ctx.save_for_backward(x, weight, y)
+        ctx.stride, ctx.packs, ctx.mode = int(stride), ent, _OPTIONS["conv_precision"]
+        # the maxima ride on the tensor objects; kept here too for a saved tensor that comes back as another
+        # object.  ``amax_of`` checks their generation and replaces a stale one by a fresh pass.
+        ctx.amax = (getattr(x, "_dsm_amax", None), getattr(y, "_dsm_amax", None))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        mode = _OPTIONS["conv_precision"]
+        _OPTIONS["conv_precision"] = ctx.mode          # the mode the saved maxima and the forward belong to
+        try:
+            return WideConv2dReLUFunction._backward(ctx, gy)
+        finally:
+            _OPTIONS["conv_precision"] = mode
+
+    @staticmethod
+    def _backward(ctx, gy):
+        x, weight, y = ctx.saved_tensors
+        for t, slot in zip((x, y), ctx.amax):
+            if slot is not None and getattr(t, "_dsm_amax", None) is None:
+                t._dsm_amax = slot
+        stride = ctx.stride
+        cout, cin = weight.shape[0], weight.shape[1]
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        g, db = bias_relu_bwd(gy, y, need_db)
+        dx = dw = None
+        if need_dx:
+            packed = _wide_pack(ctx.packs, weight, "gradient")
+            if stride == 1:
+                dx = conv2d_block(g, packed, cin, stride=1)
+            else:
+                dx = conv2d_transposed_block(g, packed, cin, x.shape[2:])
+        if need_dw:
+            dw = _wgrad2d(x, g, stride, 1, "conv2d_wgrad_kernel<S=%d,%dx%d>" % (stride, cin, cout))
+        return dx, dw, db, None
+
+
+def wide_conv2d_relu(x, weight, bias, stride=1):
+    return WideConv2dReLUFunction.apply(x, weight, bias, int(stride))
 
 
 def bn_add_relu2d(y, gamma, beta, residual, running_mean, running_var, relu, momentum, eps):

@@ -1002,7 +1002,7 @@ namespace {
 // flags bits 8..13 force the number of K-ranges (clamped to the 16-channel chunks there are).
 bool wide2d_units(const dsm_conv3d_args* a, WideParams* w) {
   w->B = a->B; w->Cin = a->Cin; w->Cout = a->Cout; w->Hi = a->Hi; w->Wi = a->Wi; w->Ho = a->Ho; w->Wo = a->Wo;
-  w->S = a->stride;
+  w->S = a->transposed ? 1 : a->stride;              // transposed (kind 9): the stride-1 geometry over Ho x Wo
   if (!dsmk::wide2d_geometry(*w)) return false;
   // at most eight chunks (216 MFMA roundings of the fp32 accumulator) per range: the tower layers hold the
   // f16x2 error band with chains of 540; a 64-chunk chain (conv6b unsplit, 1,728) would leave it
@@ -1038,6 +1038,23 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
   const int kd = a->kd ? a->kd : 3, k = a->k ? a->k : 3, dil = a->dil ? a->dil : 1;
   DSM_REQUIRE((kd == 1 || kd == 3) && (k == 1 || k == 3) && (dil == 1 || dil == 2),
               DSM_ERR_UNSUPPORTED);
+  if (kd == 1 && a->transposed) {
+    // the one transposed 2-D plan: backward-data of the stride-2 wide layers (conv_wide2d.hpp, TR).  y is the
+    // stride-1 convolution of the zero-interleaved x over Ho x Wo, 2 Hi - 1 <= Ho <= 2 Hi (the extent of the
+    // tensor whose gradient this is); fp16 modes only, no skip input
+    DSM_REQUIRE(k == 3 && dil == 1 && a->stride == 2 && a->Di == 1 && a->Do == 1 &&
+                wide2d_layer(a->Cin, a->Cout, kd, k) && !a->vol_virtual && !a->residual, DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(a->Ho <= 2 * a->Hi && a->Wo <= 2 * a->Wi &&
+                a->Ho >= 2 * a->Hi - 1 && a->Wo >= 2 * a->Wi - 1, DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(a->precision != DSM_PREC_F32 && bf16x3_enabled(a), DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(4ul * a->B * a->Hi * a->Wi * a->Cin < 0x80000000ul &&
+                (unsigned long)a->B * a->Ho * a->Wo * a->Cout < 0x7fffffffUL, DSM_ERR_UNSUPPORTED);
+    WideParams w;
+    DSM_REQUIRE(wide2d_units(a, &w), DSM_ERR_UNSUPPORTED);
+    *pl = Plan{9, 2, w.nwn, w.nunits, 16, 1, 3, 1};
+    pl->nsplit = w.ksplit;
+    return DSM_OK;
+  }
   DSM_REQUIRE(kd == 3 ? (k == 3 && dil == 1) : (!a->transposed && a->Di == 1 && a->Cout != 1),
               DSM_ERR_UNSUPPORTED);
   // natural output size; the caller may ask for a smaller corner (crop-add), never more
@@ -1165,7 +1182,7 @@ fp32_kernels:
 int make_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
   const int rc = select_plan_f32(a, pl);
   if (rc != DSM_OK) return rc;
-  if (pl->kind != 7 && pl->kind != 8) {                  // 32-bit buffer offsets (kinds 7 / 8 bound theirs above)
+  if (pl->kind != 7 && pl->kind != 8 && pl->kind != 9) { // 32-bit buffer offsets (kinds 7 / 8 / 9 bound theirs above)
     const int kd = a->kd ? a->kd : 3, k = a->k ? a->k : 3;
     DSM_REQUIRE(4ul * a->B * a->Di * a->Hi * a->Wi * a->Cin < (1ul << 32) &&
                 4ul * a->Cin * a->Cout * kd * k * k < (1ul << 32), DSM_ERR_UNSUPPORTED);
@@ -1178,7 +1195,7 @@ int make_plan(const dsm_conv3d_args* a, Plan* pl) {
   const int rc = make_plan_f32(a, pl);
   if (rc != DSM_OK) return rc;
   pl->pm = 3;
-  if ((pl->kind == 5 || pl->kind == 6 || pl->kind == 7 || pl->kind == 8) && a->precision != DSM_PREC_F32) {
+  if ((pl->kind == 5 || pl->kind == 6 || pl->kind == 7 || pl->kind == 8 || pl->kind == 9) && a->precision != DSM_PREC_F32) {
     DSM_REQUIRE(a->x_amax != nullptr, DSM_ERR_ARG);      // the input's absolute maximum (device scalar)
     pl->pm = a->precision == DSM_PREC_F16X2 ? 2 : 1;
   }
@@ -1217,6 +1234,7 @@ extern "C" int dsm_conv3d_plan(const dsm_conv3d_args* a, char* buf, int len) {
       break;
     }
     case 8: snprintf(buf, len, "conv2d_wide_%s_mfma_kernel<S=%d,N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", pl.S, 32 * pl.NT, pl.nsplit, pl.TM); break;
+    case 9: snprintf(buf, len, "deconv2d_wide_%s_mfma_kernel<N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", 32 * pl.NT, pl.nsplit, pl.TM); break;
     case 7: snprintf(buf, len, "conv3d_zs_%s_mfma_kernel%s", pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), a->vol_virtual ? "<vol>" : ""); break;
     case 6: snprintf(buf, len, "deconv3d_%s%s_mfma_kernel<NT=%d>", pl.zs ? "zs_" : "",
                      pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), pl.NT); break;
@@ -1251,7 +1269,7 @@ extern "C" int dsm_basicblock2d_fwd(const dsm_basicblock2d_args* a, dsm_stream_t
 
 extern "C" size_t dsm_conv3d_workspace_bytes(const dsm_conv3d_args* a) {
   Plan pl;
-  if (make_plan_f32(a, &pl) != DSM_OK || pl.kind != 8 || pl.nsplit <= 1) return 0;
+  if (make_plan_f32(a, &pl) != DSM_OK || (pl.kind != 8 && pl.kind != 9) || pl.nsplit <= 1) return 0;
   return (size_t)pl.nsplit * a->B * a->Ho * a->Wo * a->Cout * sizeof(float);
 }
 
@@ -1259,7 +1277,7 @@ extern "C" int dsm_conv3d_fwd(const dsm_conv3d_args* a, dsm_stream_t stream) {
   Plan pl;
   int rc = make_plan(a, &pl);
   if (rc != DSM_OK) return rc;
-  if (pl.kind == 8) {
+  if (pl.kind == 8 || pl.kind == 9) {
     WideParams w;
     wide2d_units(a, &w);
     const size_t need = dsm_conv3d_workspace_bytes(a);
@@ -1275,7 +1293,7 @@ extern "C" int dsm_conv3d_fwd(const dsm_conv3d_args* a, dsm_stream_t stream) {
     int grid = (a->flags >> DSM_CONV_BLOCKS_SHIFT) & 0xffff;      // forced grid: the units are walked in a loop
     if (grid <= 0 || grid > w.nunits) grid = w.nunits;
     dsm_clear_stale_error();
-    return dsmk::run_wide2d_f16(pl.pm, w, grid, (hipStream_t)stream);
+    return dsmk::run_wide2d_f16(pl.pm, w, grid, pl.kind == 9, (hipStream_t)stream);
   }
   ConvParams p;
   p.x = (const float*)a->x; p.w = (const float*)a->w_packed; p.scale = a->scale;

@@ -492,13 +492,23 @@ __global__ void wgrad_permute_kernel(const float* __restrict__ ws, float* __rest
   dw[i] = ws[(((long)pair * ntap + tap) * 32 + (c & 31)) * 32 + (g & 31)];
 }
 
+// The workspace is zeroed by a kernel, not by hipMemsetAsync: captured into a hipGraph, the memset node left
+// the workspace unzeroed from the second replay on (dW of a replayed step came out wrong; the first replay and
+// eager calls were right), a kernel node replays like every other launch here.
+__global__ __launch_bounds__(256) void wgrad_zero_kernel(float* __restrict__ ws, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) ws[i] = 0.f;
+}
+inline void wgrad_zero(float* ws, long n, hipStream_t s) {
+  const long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(wgrad_zero_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, ws, n);
+}
+
 template <int PM, int S, int TY, int KZ, int DIL>
 int launch_wgrad_split(WgradParams p, float* dw, int force_bx, hipStream_t s) {
   using G = WgradGeo<S, TY, KZ, DIL, WPrec<PM>::NP>;
   static_assert(G::LDS <= 160 * 1024, "LDS");
   static_assert(KZ == 3 || (TY * 2) % 4 == 0, "KZ = 1 splits the k-blocks over the four waves");
-  const size_t wsbytes = (size_t)p.npair * G::NTAP * 32 * 32 * sizeof(float);
-  if (hipMemsetAsync(p.ws, 0, wsbytes, s) != hipSuccess) return DSM_ERR_LAUNCH;
+  wgrad_zero(p.ws, (long)p.npair * G::NTAP * 32 * 32, s);
   p.ntx = dsm_cdiv(p.Wg, 32); p.nty = dsm_cdiv(p.Hg, TY);
   const long nt = (long)p.B * p.Dg * p.nty * p.ntx;
   DSM_REQUIRE(nt < (1L << 30), DSM_ERR_UNSUPPORTED);
@@ -526,8 +536,7 @@ int launch_wgrad(WgradParams p, float* dw, int force_bx, hipStream_t s) {
   constexpr int NTAP = 9 * KZ;
   constexpr size_t lds = (size_t)(KZ * IY * IX * 8 + TY * 32 * 8) * 16;
   static_assert(lds <= 160 * 1024, "LDS");
-  const size_t wsbytes = (size_t)p.npair * NTAP * 32 * 32 * sizeof(float);
-  if (hipMemsetAsync(p.ws, 0, wsbytes, s) != hipSuccess) return DSM_ERR_LAUNCH;
+  wgrad_zero(p.ws, (long)p.npair * NTAP * 32 * 32, s);
   p.ntx = dsm_cdiv(p.Wg, 32); p.nty = dsm_cdiv(p.Hg, TY);
   const long nt = (long)p.B * p.Dg * p.nty * p.ntx;
   DSM_REQUIRE(nt < (1L << 30), DSM_ERR_UNSUPPORTED);

@@ -26,7 +26,8 @@ struct ConvParams {
 
 // One place decides the kernel variant; dsm_conv3d_fwd launches it, dsm_conv3d_plan names it.
 // kind: 0 conv, 1 deconv, 2 conv cout1, 3 deconv cout1, 4 conv cout1 z-sliding, 5 conv split (bf16x3 / f16x2 / f16), 6 deconv split,
-//       7 z-sliding conv (Cout = 32, stride 1; conv_zs.hpp), 8 wide 2-D conv (Cout 256 / 512 / 1024; conv_wide2d.hpp)
+//       7 z-sliding conv (Cout = 32, stride 1; conv_zs.hpp), 8 wide 2-D conv (Cout 256 / 512 / 1024; conv_wide2d.hpp),
+//       9 its transposed mode (stride 2; backward-data of the stride-2 wide layers)
 // zs (kind 6, fp16 modes): the z-sliding transposed convolution (deconv_zs.hpp) instead of deconv_split_kernel
 struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int pm = 3; int once = 0; int zs = 0; };
 
@@ -50,7 +51,7 @@ struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int p
   X(1, 4, 1, 1, 1) X(1, 2, 1, 1, 1) X(2, 2, 1, 1, 1) X(2, 1, 1, 1, 1) X(4, 2, 1, 1, 1) X(4, 2, 1, 2, 1) \
   X(1, 2, 1, 1, 2) X(2, 2, 1, 1, 2) X(1, 1, 3, 1, 2) X(1, 1, 3, 1, 4)
 
-// Is the kernel variant that `pl` selects compiled?  (Kinds 2, 3, 4, 7, 8 are single kernels.)
+// Is the kernel variant that `pl` selects compiled?  (Kinds 2, 3, 4, 7, 8, 9 are single kernels.)
 inline bool plan_compiled(const Plan& pl) {
   switch (pl.kind) {
     case 0:
@@ -136,7 +137,7 @@ struct WideParams {
   float* y;
   float* ws;                    // [ksplit][B*Ho*Wo][Cout] partial sums (ksplit > 1)
   const float* x_amax; const float* w_amax; float* y_amax;
-  int B, Cin, Cout, Hi, Wi, Ho, Wo, S, relu;
+  int B, Cin, Cout, Hi, Wi, Ho, Wo, S, relu;     // kind 9: S = 1 over Ho x Wo, Hi x Wi the extent of x itself
   int R, CW, nby, nbx;          // M-block: R output rows x CW columns; blocks per image
   int IY, IX, XP, XE;           // input box rows / columns, LDS row pitch in slots, even-column count (S = 2)
   int nwn, ncol;                // 32-channel output blocks per workgroup (2 | 1), N-columns = Cout / (32 nwn)
@@ -167,7 +168,7 @@ inline bool wide2d_geometry(WideParams& p) {
   }
   return best >= 0;
 }
-__attribute__((visibility("hidden"))) int run_wide2d_f16(int pm, const WideParams& p, int grid, hipStream_t s);
+__attribute__((visibility("hidden"))) int run_wide2d_f16(int pm, const WideParams& p, int grid, int transposed, hipStream_t s);
 
 }  // namespace dsmk
 

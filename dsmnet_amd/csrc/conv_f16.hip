@@ -39,7 +39,12 @@ int dsmk::run_basicblock_f16(int pm, const BbParams& p, hipStream_t s) {
   return DSM_ERR_UNSUPPORTED;
 }
 
-int dsmk::run_wide2d_f16(int pm, const WideParams& p, int grid, hipStream_t s) {
+int dsmk::run_wide2d_f16(int pm, const WideParams& p, int grid, int transposed, hipStream_t s) {
+  if (transposed) {
+    if (pm == 2) return launch_conv_wide2d<2, true>(p, grid, s);
+    if (pm == 1) return launch_conv_wide2d<1, true>(p, grid, s);
+    return DSM_ERR_UNSUPPORTED;
+  }
   if (pm == 2) return launch_conv_wide2d<2>(p, grid, s);
   if (pm == 1) return launch_conv_wide2d<1>(p, grid, s);
   return DSM_ERR_UNSUPPORTED;

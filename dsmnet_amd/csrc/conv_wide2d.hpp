@@ -44,7 +44,11 @@ struct WideCfg {
   static_assert(LDS <= 160 * 1024, "LDS");
 };
 
-template <int PM>
+// TR: the transposed mode (plan kind 9, backward-data of the stride-2 layers).  The launch is the stride-1
+// kernel over the Ho x Wo map X' with X'[2i][2j] = x[i][j] and zeros elsewhere (p.S = 1, p.Hi x p.Wi the
+// extent of x itself): only the staging address differs -- a slot whose ABSOLUTE coordinate is even in both
+// directions loads x[y/2][x/2], every other slot takes the out-of-range offset.
+template <int PM, bool TR = false>
 __global__ __launch_bounds__(512, 2) void conv_wide2d_kernel(WideParams p) {
   using Cf = WideCfg<PM>;
   using frag = typename Prec<PM>::frag;
@@ -97,8 +101,13 @@ __global__ __launch_bounds__(512, 2) void conv_wide2d_kernel(WideParams p) {
       const int yy = slot / p.XP, xs = slot % p.XP;
       const int xx = p.S == 2 ? (xs < p.XE ? 2 * xs : 2 * (xs - p.XE) + 1) : xs;
       const int y = y0 * p.S - 1 + yy, x = x0 * p.S - 1 + xx;
-      const bool ok = yy < p.IY && xx < p.IX && (unsigned)y < (unsigned)p.Hi && (unsigned)x < (unsigned)p.Wi;
-      voff[k] = ok ? (unsigned)(4l * ((((long)b * p.Hi + y) * p.Wi + x) * p.Cin + 4 * q)) : OOBV;
+      if constexpr (TR) {
+        const bool ok = yy < p.IY && xx < p.IX && y >= 0 && x >= 0 && !((y | x) & 1) && (y >> 1) < p.Hi && (x >> 1) < p.Wi;
+        voff[k] = ok ? (unsigned)(4l * ((((long)b * p.Hi + (y >> 1)) * p.Wi + (x >> 1)) * p.Cin + 4 * q)) : OOBV;
+      } else {
+        const bool ok = yy < p.IY && xx < p.IX && (unsigned)y < (unsigned)p.Hi && (unsigned)x < (unsigned)p.Wi;
+        voff[k] = ok ? (unsigned)(4l * ((((long)b * p.Hi + y) * p.Wi + x) * p.Cin + 4 * q)) : OOBV;
+      }
     }
     // ---- this wave's M-tiles mg, mg + MG, ...: each lane's pixel
     int xb[MT], opix[MT];
@@ -227,16 +236,16 @@ __global__ __launch_bounds__(256) void wide2d_reduce_kernel(WideParams p) {
   flush_amax(p.y_amax, am, red);
 }
 
-template <int PM>
+template <int PM, bool TR = false>
 int launch_conv_wide2d(const WideParams& p, int grid, hipStream_t s) {
   using Cf = WideCfg<PM>;
   static thread_local bool configured = false;
   if (!configured) {
-    if (hipFuncSetAttribute((const void*)conv_wide2d_kernel<PM>, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)conv_wide2d_kernel<PM, TR>, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS) != hipSuccess)
       return DSM_ERR_LAUNCH;
     configured = true;
   }
-  hipLaunchKernelGGL(conv_wide2d_kernel<PM>, dim3((unsigned)grid), dim3(Cf::THREADS), Cf::LDS, s, p);
+  hipLaunchKernelGGL((conv_wide2d_kernel<PM, TR>), dim3((unsigned)grid), dim3(Cf::THREADS), Cf::LDS, s, p);
   if (p.ksplit > 1) {
     const long nq = (long)p.B * p.Ho * p.Wo * (p.Cout >> 2);
     const long blocks = dsm_cdiv(nq, 256);

@@ -52,8 +52,10 @@ class Conv2dReLU(nn.Sequential):
     reference's child indices.  Eval mode, no autograd, fp32 on the GPU, the option ``wide_conv2d`` on,
     an fp16 precision mode and a layer ``blocks2d.fused_ok`` admits with 256 / 512 / 1024 outputs:
     convolution + bias + ReLU as one op on the wide MFMA kernel (NHWC in and out, the output carries
-    its absolute maximum for the next layer).  Everything else -- training, CPU tensors, k 5 / 7, odd
-    Cin, the narrower layers -- runs the two children as before."""
+    its absolute maximum for the next layer).  Under autograd with the option ``wide_conv2d_train`` on, the
+    layers with Cin and Cout both in 256 / 512 / 1024 run ``costvolume.wide_conv2d_relu`` (explicit gradients on
+    the HIP kernels, NHWC).  Everything else -- CPU tensors, k 5 / 7, odd Cin, the narrower layers, training
+    with that option off -- runs the two children as before."""
 
     def __init__(self, conv, act):
         super(Conv2dReLU, self).__init__(conv, act)
@@ -61,6 +63,11 @@ class Conv2dReLU(nn.Sequential):
 
     def forward(self, x):
         conv = self[0]
+        if (cv.get_option("wide_conv2d_train") and torch.is_grad_enabled() and
+                (x.requires_grad or conv.weight.requires_grad or (conv.bias is not None and conv.bias.requires_grad))):
+            from ..blocks2d import wide_train_ok
+            if wide_train_ok(conv, self[1], x):
+                return cv.wide_conv2d_relu(x, conv.weight, conv.bias, conv.stride[0])
         if (not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and
                 conv.out_channels in cv.WIDE2D_COUT and cv.get_option("wide_conv2d") and cv.needs_amax() and
                 isinstance(self[1], nn.ReLU)):

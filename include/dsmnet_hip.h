@@ -304,6 +304,30 @@ size_t dsm_conv3d_workspace_bytes(const dsm_conv3d_args* args);
  * which no extent under the plan's 4 GiB bound reaches. */
 int dsm_conv3d_plan(const dsm_conv3d_args* args, char* buf, int len);
 
+/* (ABI v7, additive) The transposed mode of the wide 2-D kernel: backward-data of the stride-2 wide layers.
+ * dsm_conv3d_args with kd = 1, k = 3, dil = 1, transposed = 1, stride = 2, Cout = 256 | 512 | 1024,
+ * Cin % 16 == 0, precision DSM_PREC_F16X2 | DSM_PREC_F16 (else DSM_ERR_UNSUPPORTED, as for the wide layers;
+ * every other transposed 2-D request stays DSM_ERR_UNSUPPORTED).  x: (B, Hi, Wi, Cin) NHWC; y: (B, Ho, Wo, Cout)
+ * with 2 Hi - 1 <= Ho <= 2 Hi and 2 Wi - 1 <= Wo <= 2 Wi -- the extent of the tensor whose gradient this is.
+ * With X' the zero-interleaved map of Ho x Wo (X'[2i][2j] = x[i][j], zero elsewhere):
+ *   y = conv2d(X', w_packed, stride 1, pad 1), then scale / shift / ReLU and y_amax as usual,
+ * which equals conv_transpose2d(x, W, stride 2, padding 1, output_padding 1)[:, :, :Ho, :Wo] when w_packed
+ * holds the 180-degree-flipped, in/out-transposed W (dsm_conv_pack_weights, Cin = this Cin, Cout = this Cout).
+ * Runs on "deconv2d_wide_<f16x2|f16>_mfma_kernel<N,KS=K,units>": the stride-1 work decomposition over
+ * Ho x Wo, the same K ranges, `workspace` ([K][B*Ho*Wo][Cout] floats, dsm_conv3d_workspace_bytes) and the
+ * same deterministic second launch; x_amax is required. */
+
+/* (ABI v7, additive) Backward of bias + ReLU behind a wide layer, NHWC tensors viewed as [M][C], C % 4 == 0:
+ *   g[m][c] = y[m][c] > 0 ? gy[m][c] : 0   (g is a tensor of its own; gy is never written)
+ *   db[c]   = sum_m g[m][c]                (db may be NULL)
+ *   *g_amax = max(*g_amax, max |g|)        (folded like y_amax of the convolutions; may be NULL)
+ * One pass of 12 bytes per element plus a small second launch for db.  db is summed in a fixed order
+ * (per-workgroup partial sums in `ws`, plain stores, then added in index order; no float atomics): two
+ * runs give the same bits.  ws: min(512, ceil(M / 8)) * C floats -- 512 * C always suffices -- 16-byte
+ * aligned; not read when db is NULL.  All tensors 16-byte aligned. */
+int dsm_bias_relu_bwd(const void* gy, const void* y, void* g, void* db, void* ws, float* g_amax,
+                      long M, int C, dsm_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Backward of the 3-D convolution blocks (training through the trunk; in the reference this
  * is autograd through nn.Conv3d / nn.ConvTranspose3d).  bwd-data is a convolution again and

@@ -85,8 +85,8 @@ def layer_rows(reps):
         a.x = a.w_packed = a.y = a.x_amax = 16
         a.B, a.Cin, a.Cout, a.Di, a.Hi, a.Wi, a.Do, a.Ho, a.Wo = 1, cin, cout, 1, H, W, 1, Ho, Wo
         a.stride, a.kd, a.k, a.dil, a.precision = s, 1, 3, 1, cv._lib.DSM_PREC_F16X2
-        rows.append((name, cin, cout, s, "%dx%d" % (Ho, Wo), gflop, t_stock, t_wide, gflop / t_wide * 1e-3,
-                     gflop / t_wide * 1e-3 / (2500.0 / 3), wbytes / t_wide * 1e-6, wbytes / t_wide * 1e-6 / 6.3,
+        rows.append((name, cin, cout, s, "%dx%d" % (Ho, Wo), gflop, t_stock, t_wide, gflop / t_wide * 1e3,
+                     gflop / t_wide * 1e3 / (2500.0 / 3), wbytes / t_wide * 1e-6, wbytes / t_wide * 1e-6 / 6.3,
                      err, cv.conv3d_plan_name(a)))
     return rows
 
