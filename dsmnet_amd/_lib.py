@@ -125,6 +125,8 @@ SIGNATURES = {
     "dsm_spp_branches": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     "dsm_spp_concat": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 2),
     "dsm_warp_abs_error": (c_int, [c_void_p] * 4 + [c_int] * 6 + [ctypes.c_float, c_void_p]),
+    "dsm_warp_abs_error_bwd": (c_int, [c_void_p] * 7 + [c_int] * 6 + [ctypes.c_float, c_void_p]),
+    "dsm_decoder_cat_bwd": (c_int, [c_void_p] * 6 + [c_int] * 11 + [c_void_p]),
     "dsm_selfsup_workspace_floats": (c_size_t, [ctypes.POINTER(SelfsupItem), c_int]),
     "dsm_selfsup_fwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
     "dsm_selfsup_bwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),

@@ -471,7 +471,9 @@ _OPTIONS = {"fuse_volume": True, "fuse_blocks": True, "conv_precision": _env_pre
             "separable_volume": _env_flag("DSM_SEPARABLE_VOLUME", True), "separable_flags": 0,
             "fused_supervised_loss": _env_flag("DSM_FUSED_SUP_LOSS", True),
             "wide_conv2d": _env_flag("DSM_WIDE_CONV2D", _WIDE_CONV2D_DEFAULT),
-            "wide_conv2d_train": _env_flag("DSM_WIDE_CONV2D_TRAIN", False)}
+            "wide_conv2d_train": _env_flag("DSM_WIDE_CONV2D_TRAIN", False),
+            "warp_train": _env_flag("DSM_WARP_TRAIN", False),
+            "decoder_train": _env_flag("DSM_DECODER_TRAIN", False)}
 
 
 def set_option(name, value):
@@ -498,6 +500,12 @@ def set_option(name, value):
     ``wide_conv2d_relu`` under autograd (forward, ReLU + bias backward, backward-data and weight gradient on
     this project's kernels; fp16 modes), whatever ``wide_conv2d`` says; default off (profiles/wide2d_train.md),
     starts from DSM_WIDE_CONV2D_TRAIN=0|1;
+    ``warp_train`` -- iResNet's reconstruction error ``|stemL - imwrap_BCHW(stemR, -r_pr0)|`` runs as
+    ``warp_abs_error`` under autograd too (fp32 GPU tensors; csrc/warp.hip forward and backward) instead of the
+    stock grid_sample chain; default off (profiles/train_ops.md), starts from DSM_WARP_TRAIN=0|1;
+    ``decoder_train`` -- ``decoder_level`` keeps its one-launch bias + ReLU + upsampling + concatenation under
+    autograd (``DecoderCatFunction``, csrc/decoder.hip forward and backward); independent of ``warp_train``;
+    default off (profiles/train_ops.md), starts from DSM_DECODER_TRAIN=0|1;
     ``conv_flags`` -- raw dsm_conv3d_args.flags bits (tile height, grid size, K-ranges of the wide layers)."""
     if name == "conv_fp32":
         old = _OPTIONS["conv_precision"] == "fp32"
@@ -1004,7 +1012,14 @@ def basicblock2d(x, packed1, scale1, shift1, packed2, scale2, shift2, relu=False
 def warp_abs_error(left, right, disp, delt):
     """``|left - imwrap_BCHW(right, disp)|`` in one pass (csrc/warp.hip; utils/imwrap.py:37-72,
     models/iresnet.py:169-170).  ``left=None``: the warped map itself.  ``delt`` is the
-    reference's random epsilon (a Python float drawn by the caller).  NCHW fp32; inference only."""
+    reference's random epsilon (a Python float drawn by the caller).  NCHW fp32.  With autograd on and
+    an input that requires grad, the same launch runs inside ``WarpAbsErrorFunction``."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (left, right, disp)):
+        return WarpAbsErrorFunction.apply(left, right, disp, float(delt))
+    return _warp_abs_error_fwd(left, right, disp, delt)
+
+
+def _warp_abs_error_fwd(left, right, disp, delt):
     _require_device("warp_abs_error", right, disp, left)
     B, C, H0, W0 = right.shape
     if disp.dim() != 4 or disp.shape[0] != B or disp.shape[1] != 1:
@@ -1025,6 +1040,38 @@ def warp_abs_error(left, right, disp, delt):
                                             _p(out), B, C, H, W, H0, W0, float(delt), _stream())
     _lib.check(rc, "dsm_warp_abs_error")
     return out
+
+
+class WarpAbsErrorFunction(torch.autograd.Function):
+    """``warp_abs_error`` under autograd.  The forward is the eval launch (the same bits); the backward is
+    one call of ``dsm_warp_abs_error_bwd``, which recomputes the warp from the saved inputs: ``gL`` and
+    ``gdisp`` are written by one thread each, ``gR`` is an fp32 atomic scatter into a buffer the call zeroes."""
+
+    @staticmethod
+    def forward(ctx, left, right, disp, delt):
+        out = _warp_abs_error_fwd(left, right, disp, delt)
+        ctx.has_left, ctx.delt = left is not None, float(delt)
+        ctx.save_for_backward(right.contiguous(), disp.contiguous(), *([left.contiguous()] if ctx.has_left else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        right, disp = ctx.saved_tensors[:2]
+        left = ctx.saved_tensors[2] if ctx.has_left else None
+        need_l, need_r, need_d = ctx.needs_input_grad[:3]
+        B, C, H0, W0 = right.shape
+        H, W = disp.shape[2:]
+        g = g.contiguous()
+        gl = torch.empty_like(left) if (need_l and ctx.has_left) else None
+        gr = torch.empty_like(right) if need_r else None          # zeroed by the call
+        gd = torch.empty_like(disp) if need_d else None
+        work = 4.0 * (g.numel() * (1 + int(ctx.has_left) + int(gl is not None)) + right.numel() + disp.numel() +
+                      (2 * right.numel() if need_r else 0) + (disp.numel() if need_d else 0))   # gR: zeroed, summed
+        with torch.cuda.device(right.device), _timed("warp_abs_error_bwd_kernel", work):
+            rc = _lib.load().dsm_warp_abs_error_bwd(_p(g), _p(left), _p(right), _p(disp), _p(gl), _p(gr), _p(gd),
+                                                    B, C, H, W, H0, W0, ctx.delt, _stream())
+        _lib.check(rc, "dsm_warp_abs_error_bwd")
+        return gl, gr, gd, None
 
 
 def spp_head(raw, skip, w_t, scale, shift):
@@ -1491,13 +1538,14 @@ def decoder_level(deconv, x, pr, skip):
     ``deconv`` = ``Sequential(ConvTranspose2d(bias), ReLU)`` or a bare ``ConvTranspose2d``.
     Eval mode on the GPU: the transposed convolution runs without its bias (stock kernel) and ONE
     launch does bias + ReLU + bilinear x2 upsampling of ``pr`` + the crops + the concatenation;
-    otherwise (training, autograd, CPU) the stock ops."""
+    under autograd the same with the option ``decoder_train`` on (``DecoderCatFunction``: the transposed
+    convolution stays a stock autograd node); otherwise (training, autograd, CPU) the stock ops."""
     import torch.nn as nn
     import torch.nn.functional as F
     conv = deconv[0] if isinstance(deconv, nn.Sequential) else deconv
     relu = isinstance(deconv, nn.Sequential) and len(deconv) > 1
-    fast = (x.is_cuda and not torch.is_grad_enabled() and x.dtype == torch.float32 and
-            isinstance(conv, nn.ConvTranspose2d) and
+    fast = (x.is_cuda and (not torch.is_grad_enabled() or _OPTIONS["decoder_train"]) and
+            x.dtype == torch.float32 and isinstance(conv, nn.ConvTranspose2d) and
             (not relu or (len(deconv) == 2 and isinstance(deconv[1], nn.ReLU))))
     if not fast:
         seq = [deconv(x)]
@@ -1510,6 +1558,12 @@ def decoder_level(deconv, x, pr, skip):
         return torch.cat([t[:, :, :h, :w] for t in seq], dim=1)
     up = F.conv_transpose2d(x, conv.weight, None, conv.stride, conv.padding, conv.output_padding,
                             conv.groups, conv.dilation).contiguous()
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (up, conv.bias, pr, skip)):
+        return DecoderCatFunction.apply(up, conv.bias, pr, skip, bool(relu))
+    return _decoder_cat_fwd(up, conv.bias, pr, skip, relu)
+
+
+def _decoder_cat_fwd(up, bias, pr, skip, relu):
     B, Cu, Hu, Wu = up.shape
     pr = None if pr is None else pr.contiguous()
     skip = None if skip is None else skip.contiguous()
@@ -1517,12 +1571,50 @@ def decoder_level(deconv, x, pr, skip):
     Cs, Hs, Ws = (0, 0, 0) if skip is None else skip.shape[1:]
     h = min([Hu] + ([2 * Hp] if Cp else []) + ([Hs] if Cs else []))
     w = min([Wu] + ([2 * Wp] if Cp else []) + ([Ws] if Cs else []))
-    out = torch.empty((B, Cu + Cp + Cs, h, w), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device), _timed("decoder_cat_kernel", 8.0 * out.numel()):
-        rc = _lib.load().dsm_decoder_cat(_p(up), _p(conv.bias), _p(pr), _p(skip), _p(out), B, Cu, Cp, Cs,
+    out = torch.empty((B, Cu + Cp + Cs, h, w), device=up.device, dtype=torch.float32)
+    with torch.cuda.device(up.device), _timed("decoder_cat_kernel", 8.0 * out.numel()):
+        rc = _lib.load().dsm_decoder_cat(_p(up), _p(bias), _p(pr), _p(skip), _p(out), B, Cu, Cp, Cs,
                                          Hu, Wu, Hp, Wp, Hs, Ws, int(relu), _stream())
     _lib.check(rc, "dsm_decoder_cat")
     return out
+
+
+class DecoderCatFunction(torch.autograd.Function):
+    """``relu?(up + bias) | upsample_x2(pr) | skip`` of ``decoder_level`` under autograd: ``up`` is the stock
+    transposed convolution's output without its bias.  Only the output is saved (the following ``iconv`` keeps
+    it anyway): its first ``Cu`` channels are the ReLU mask.  The backward is one call of
+    ``dsm_decoder_cat_bwd``; ``g_bias`` is the only gradient summed with atomics."""
+
+    @staticmethod
+    def forward(ctx, up, bias, pr, skip, relu):
+        out = _decoder_cat_fwd(up.contiguous(), bias, pr, skip, relu)
+        ctx.relu = bool(relu)
+        ctx.shapes = (tuple(up.shape), None if pr is None else tuple(pr.shape),
+                      None if skip is None else tuple(skip.shape))
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        out, = ctx.saved_tensors
+        su, sp, ss = ctx.shapes
+        need_up, need_b, need_pr, need_skip = ctx.needs_input_grad[:4]
+        B, Cu, Hu, Wu = su
+        Cp, Hp, Wp = (0, 0, 0) if sp is None else sp[1:]
+        Cs, Hs, Ws = (0, 0, 0) if ss is None else ss[1:]
+        g = g.contiguous()
+
+        def new(shape, need):
+            return torch.empty(shape, device=g.device, dtype=torch.float32) if need else None
+        g_up, g_b = new(su, need_up), new((Cu,), need_b)
+        g_pr, g_skip = new(sp, need_pr and Cp > 0), new(ss, need_skip and Cs > 0)
+        work = 4.0 * sum(t.numel() for t in (g_up, g_pr, g_skip) if t is not None) * 2 + \
+            (4.0 * B * Cu * out.shape[2] * out.shape[3] if ctx.relu else 0.0)
+        with torch.cuda.device(g.device), _timed("decoder_cat_bwd_kernel", work):
+            rc = _lib.load().dsm_decoder_cat_bwd(_p(g), _p(out), _p(g_up), _p(g_b), _p(g_pr), _p(g_skip),
+                                                 B, Cu, Cp, Cs, Hu, Wu, Hp, Wp, Hs, Ws, int(ctx.relu), _stream())
+        _lib.check(rc, "dsm_decoder_cat_bwd")
+        return g_up, g_b, g_pr, g_skip, None
 
 
 # ----------------------------------------------------------------------------

@@ -2,8 +2,8 @@
 as models/dispnetcorr.py; `self.corr` is the HIP Corr1d (D=41); the encoder's seven 3x3 layers of
 256 / 512 / 1024 channels (conv3b .. conv6b) run on the wide MFMA kernel in eval mode when the
 `costvolume` option `wide_conv2d` is on (csrc/conv_wide2d.hpp, `util_conv.Conv2dReLU`); each decoder
-level's bias + ReLU + upsampling + myCat2d is one HIP launch in eval mode (`costvolume.decoder_level`,
-csrc/decoder.hip); the stems, conv3a, the iconv / deconv layers and the heads are the reference's stock
+level's bias + ReLU + upsampling + myCat2d is one HIP launch in eval mode, and under autograd with the option
+`decoder_train` (`costvolume.decoder_level`, csrc/decoder.hip); the stems, conv3a, the iconv / deconv layers and the heads are the reference's stock
 2-D layers."""
 import torch
 import torch.nn as nn

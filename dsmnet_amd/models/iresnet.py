@@ -34,6 +34,18 @@ def imwrap_BCHW(im_src, disp):
                          align_corners=False)
 
 
+def recon_error(stemL, stemR, r_pr0):
+    """``|stemL - imwrap_BCHW(stemR, -r_pr0)|`` (models/iresnet.py:169-170).  GPU tensors without autograd, or
+    fp32 GPU tensors under autograd with the `costvolume` option `warp_train`: one HIP pass (`warp_abs_error`;
+    forward and backward one launch each); otherwise the stock ops."""
+    if stemL.is_cuda and (not torch.is_grad_enabled() or (
+            cv.get_option("warp_train") and stemL.dtype == stemR.dtype == r_pr0.dtype == torch.float32)):
+        # the epsilon is drawn exactly as the reference draws it (imwrap.py:70)
+        delt = float(1e-4 * (torch.rand(1)[0] + 0.1))
+        return cv.warp_abs_error(stemL, stemR, -r_pr0, delt)
+    return torch.abs(stemL - imwrap_BCHW(stemR, -r_pr0))
+
+
 _ENCODER = [("conv3", 81 + 64, 256, 2), ("conv3_1", 256, 256, 1), ("conv4", 256, 512, 2),
             ("conv4_1", 512, 512, 1), ("conv5", 512, 512, 2), ("conv5_1", 512, 512, 1),
             ("conv6", 512, 1024, 2), ("conv6_1", 1024, 1024, 1)]
@@ -118,12 +130,7 @@ class iresnet(nn.Module):
             out_scale.insert(0, lvl)
         r_pr2, r_pr1, r_pr0 = keep[2], keep[1], keep[0]
         for _ in range(iter):
-            if stemL.is_cuda and not torch.is_grad_enabled():
-                # one HIP pass; the epsilon is drawn exactly as the reference draws it (imwrap.py:70)
-                delt = float(1e-4 * (torch.rand(1)[0] + 0.1))
-                err = cv.warp_abs_error(stemL, stemR, -r_pr0, delt)
-            else:
-                err = torch.abs(stemL - imwrap_BCHW(stemR, -r_pr0))
+            err = recon_error(stemL, stemR, r_pr0)
             r_conv0 = self.r_conv0(myCat2d(err, r_pr0, stemL))
             r_conv1 = self.r_conv1(r_conv0)
             r_corr = self.r_corr(self.c_conv1(conv1L), self.c_conv1(conv1R))

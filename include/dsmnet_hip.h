@@ -449,6 +449,20 @@ int dsm_spp_concat(const void* raw, const void* skip, const void* branches, void
 int dsm_warp_abs_error(const void* L, const void* R, const void* disp, void* out, int B, int C,
                        int H, int W, int H0, int W0, float delt, dsm_stream_t stream);
 
+/* (ABI v7, additive) Backward of dsm_warp_abs_error -- what autograd runs for utils/imwrap.py:37-72
+ * (linspace grids, stack, `im_src + delt`, grid_sample) and the sub + abs of models/iresnet.py:169-170.
+ * Same sizes and delt as the forward; nothing is saved, v is recomputed from L, R, disp bit for bit.
+ *   g (B,C,H,W): the gradient of the forward's out.  L = NULL: the plain warp (gv = g).
+ *   gL (B,C,H,W)   = g * sign(L - v)            (sign(0) = 0, as torch.abs)
+ *   gR (B,C,H0,W0) += gv * w_tap on every in-bounds tap, gv = -g * sign(L - v): fp32 atomics; zeroed
+ *                     by this call on `stream` first (the sum's last bits depend on arrival order)
+ *   gdisp (B,1,H,W) = -(W0/(W0-1)) * sum_c gv_c * (wy0 * (ne_c - nw_c) + wy1 * (se_c - sw_c)) with the
+ *                     tap values R + delt, 0 out of bounds (ATen's grid_sample backward, zeros padding)
+ * Any of gL, gR, gdisp may be NULL: that gradient is skipped.  gL and gdisp are run-to-run identical. */
+int dsm_warp_abs_error_bwd(const void* g, const void* L, const void* R, const void* disp,
+                           void* gL, void* gR, void* gdisp,
+                           int B, int C, int H, int W, int H0, int W0, float delt, dsm_stream_t stream);
+
 /* One decoder level of DispNetC / iResNet (models/dispnetcorr.py:89-132, iresnet.py:119-161,186-193):
  *   out = myCat2d( relu?(up + bias), upsample_x2_bilinear(pr), skip )      (util_fun.py:7-15)
  * up (B,Cu,Hu,Wu): the transposed convolution's output WITHOUT its bias; bias [Cu] or NULL;
@@ -458,6 +472,21 @@ int dsm_warp_abs_error(const void* L, const void* R, const void* disp, void* out
 int dsm_decoder_cat(const void* up, const void* bias, const void* pr, const void* skip, void* out,
                     int B, int Cu, int Cp, int Cs, int Hu, int Wu, int Hp, int Wp, int Hs, int Ws,
                     int relu, dsm_stream_t stream);
+
+/* (ABI v7, additive) Backward of dsm_decoder_cat -- what autograd runs for the bias add, the in-place
+ * ReLU, nn.Upsample, the three crops and torch.cat of models/dispnetcorr.py:89-132 and
+ * iresnet.py:119-161,186-193 (util_fun.py:7-15).  g and out are (B, Cu+Cp+Cs, h, w), h and w as in the
+ * forward; out is the forward's result: its first Cu channels carry the ReLU mask (out > 0), needed
+ * when relu != 0 only.
+ *   g_up (B,Cu,Hu,Wu)   = g[:, :Cu] (times the mask), zero in the cropped-off rows / columns
+ *   g_bias [Cu]         = sum of g_up over (b, y, x); one fp32 atomic per block, zeroed by this call
+ *   g_pr (B,Cp,Hp,Wp)   = the adjoint of the bilinear x2 upsampling over the h x w crop (gathered)
+ *   g_skip (B,Cs,Hs,Ws) = g[:, Cu+Cp:], zero-padded likewise
+ * Any of the four may be NULL: that gradient is skipped.  Every element of a requested gradient is
+ * written; g_up, g_pr, g_skip have one writer per element.  At most two launches. */
+int dsm_decoder_cat_bwd(const void* g, const void* out, void* g_up, void* g_bias, void* g_pr, void* g_skip,
+                        int B, int Cu, int Cp, int Cs, int Hu, int Wu, int Hp, int Wp, int Hs, int Ws,
+                        int relu, dsm_stream_t stream);
 
 /* (ABI v5) Image staging of the 2-D towers (models/psmnet/stackhourglass.py:118-121 feeds the two
  * views through feature_extraction one after the other; in eval mode they share one batch):
