@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from . import costvolume as cv
 from . import blocks3d
-from .blocks3d import _versions
+from .folds import _bump_running_stats, _versions, fold_affine
 
 # Training through the 2-D towers (DSM_TRAIN_2D, read by this host module):
 #   auto  (default) a layer runs on costvolume.Conv2dFunction (forward, backward-data and weight
@@ -129,20 +129,7 @@ class _Folded2d(object):
         if key != self.key:
             with torch.no_grad():
                 self.packed = cv.pack_conv2d_weight(conv.weight, cin_padded)
-                if bn is not None:
-                    inv = torch.rsqrt(bn.running_var + bn.eps)
-                    scale = bn.weight * inv if bn.weight is not None else inv
-                    shift = -bn.running_mean * scale
-                    if bn.bias is not None:
-                        shift = shift + bn.bias
-                    if conv.bias is not None:
-                        shift = shift + conv.bias * scale
-                    self.scale, self.shift = scale.contiguous(), shift.contiguous()
-                elif conv.bias is not None:
-                    self.scale = torch.ones_like(conv.bias)
-                    self.shift = conv.bias.detach().clone()
-                else:
-                    self.scale = self.shift = None
+                self.scale, self.shift = fold_affine(conv.bias, bn, conv.out_channels, conv.weight.device)
             self.key = key
         return self.packed, self.scale, self.shift
 
@@ -178,7 +165,7 @@ def _run_conv2d_autograd(conv, bn, x, residual, relu):
                                1 if relu else 0, momentum, bn.eps)
         if bn.num_batches_tracked is not None:
             bn.num_batches_tracked += 1
-        blocks3d._bump_running_stats(bn)      # running statistics changed through raw pointers
+        _bump_running_stats(bn)      # running statistics changed through raw pointers
         return out
     if bn is not None:
         y = bn(y)

@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import costvolume as cv
+from .folds import _EPOCH, _bump_running_stats, _versions, fold_affine, invalidate_folded_caches  # noqa: F401
 
 RELU_NONE, RELU_AFTER_ADD, RELU_BEFORE_ADD = 0, 1, 2
 _FUSED_TRAIN_BN = __import__("os").environ.get("DSM_TRAIN_BN", "fused") != "stock"
@@ -19,31 +20,6 @@ _FUSED_TRAIN_BN = __import__("os").environ.get("DSM_TRAIN_BN", "fused") != "stoc
 # in a ReLU (the sign pattern of the ReLU's input is `out > 0` for mode 1, `out > residual`, cropped to
 # out, for mode 2)
 _TRAIN_RELU_HOOK = [None]
-
-
-_EPOCH = [0]
-
-
-def invalidate_folded_caches():
-    """Drop every cached packed weight / folded BN affine (3-D blocks, 2-D blocks, SPP head):
-    they are re-made at the next forward.  The caches notice ordinary updates by themselves
-    (optimizer steps, ``load_state_dict``, ``with torch.no_grad(): w.mul_(...)`` -- all bump the
-    tensor's ``_version``); an in-place edit THROUGH ``.data`` (``w.data.mul_()``) does not, and
-    needs this call afterwards.  Exported as ``dsmnet_amd.refold()``."""
-    _EPOCH[0] += 1
-
-
-def _bump_running_stats(bn):
-    """The BN kernels update the running statistics through raw pointers: bump the two tensors'
-    version counters by hand, so that exactly the folds made from THIS layer's statistics are re-made
-    at the next eval forward (a global invalidation would re-pack every layer after every step)."""
-    if bn.track_running_stats and bn.running_mean is not None:
-        torch.autograd.graph.increment_version(bn.running_mean)
-        torch.autograd.graph.increment_version(bn.running_var)
-
-
-def _versions(*tensors):
-    return tuple((t.data_ptr(), t._version) for t in tensors if t is not None) + (_EPOCH[0],)
 
 
 class _Folded(object):
@@ -65,21 +41,7 @@ class _Folded(object):
             with torch.no_grad():
                 self.packed = cv.pack_conv3d_weight(conv.weight, transposed)
                 self.separable = None
-                cout = conv.out_channels
-                if bn is not None:
-                    inv = torch.rsqrt(bn.running_var + bn.eps)
-                    scale = bn.weight * inv if bn.weight is not None else inv
-                    shift = -bn.running_mean * scale
-                    if bn.bias is not None:
-                        shift = shift + bn.bias
-                    if conv.bias is not None:
-                        shift = shift + conv.bias * scale
-                    self.scale, self.shift = scale.contiguous(), shift.contiguous()
-                elif conv.bias is not None:
-                    self.scale = torch.ones(cout, device=conv.weight.device)
-                    self.shift = conv.bias.detach().clone()
-                else:
-                    self.scale = self.shift = None
+                self.scale, self.shift = fold_affine(conv.bias, bn, conv.out_channels, conv.weight.device)
             self.key = key
         return self.packed, self.scale, self.shift
 

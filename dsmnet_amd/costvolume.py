@@ -16,10 +16,13 @@ Reference code each op replaces (sunshinnnn/DSMnet):
   supervised_pyramid_loss   losses/loss.py:326-338, 407-421, stereo.py:103-113
 """
 import ctypes
+import os
+import weakref
 
 import torch
 
 from . import _lib
+from .folds import _versions
 
 _CL3D = torch.channels_last_3d
 
@@ -88,9 +91,11 @@ def _p(t):
 def _plan_name(fn, *args):
     """Branch name written by one of the host-only ``dsm_*_plan`` queries (include/dsmnet_hip.h).  Pointer
     arguments are tensors, raw addresses or None: only NULL-ness and 16-byte alignment are looked at, so
-    this needs no GPU.  Raises what the launch itself would be refused with."""
+    this needs no GPU.  An argument struct goes by reference.  Raises what the launch itself would be refused
+    with."""
     buf = ctypes.create_string_buffer(96)
-    conv = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+    conv = [_p(a) if isinstance(a, torch.Tensor) else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+            for a in args]
     _lib.check(getattr(_lib.load(), fn)(*(conv + [buf, 96])), fn)
     return buf.value.decode()
 
@@ -394,70 +399,49 @@ def conv3d_block(x, packed_weight, cout, scale=None, shift=None, residual=None, 
         x = carry_amax(to_channels_last_3d(x), x)
         B, cin, Di, Hi, Wi = x.shape
     Do, Ho, Wo = conv3d_out_size((Di, Hi, Wi), stride, transposed)
-    a = _lib.Conv3dArgs()
+    res_size = None
     if residual is not None:
         if residual.shape[0] != B or residual.shape[1] != cout:
             raise ValueError("conv3d_block: residual has shape %s, expected (%d,%d,...)"
                              % (tuple(residual.shape), B, cout))
         residual = to_channels_last_3d(residual)
-        a.Dr, a.Hr, a.Wr = residual.shape[2:]
-        Do, Ho, Wo = min(Do, a.Dr), min(Ho, a.Hr), min(Wo, a.Wr)
+        res_size = tuple(residual.shape[2:])
+        Do, Ho, Wo = (min(n, r) for n, r in zip((Do, Ho, Wo), res_size))
     if out_size is not None:                     # a corner of the natural output (bwd-data crops)
         Do, Ho, Wo = (min(n, int(o)) for n, o in zip((Do, Ho, Wo), out_size))
     y = torch.empty((B, cout, Do, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL3D)
-    a.x = x.data_ptr()
-    a.w_packed = packed_weight.data_ptr()
-    a.y = y.data_ptr()
-    a.scale = None if scale is None else scale.data_ptr()
-    a.shift = None if shift is None else shift.data_ptr()
-    a.residual = None if residual is None else residual.data_ptr()
-    a.B, a.Cin, a.Cout = B, cin, cout
-    a.Di, a.Hi, a.Wi = Di, Hi, Wi
-    a.Do, a.Ho, a.Wo = Do, Ho, Wo
-    a.stride, a.transposed, a.relu = int(stride), int(transposed), int(relu)
-    a.flags = _conv_flags()
-    if virtual is not None:
-        a.vol_virtual, a.vol_mask_left = 1, int(virtual.mask_left)
-    keep = _set_precision(a, x, y if cout > 1 else None)
     # FLOPs as SURVEY.md section 8d counts them: 2*27*Cin*Cout per output voxel (conv) or
     # per input voxel (transposed conv)
     # (Cout = 1 runs on the VALU and is HBM-bound: input read once + output written)
     vox = B * (Di * Hi * Wi if transposed else Do * Ho * Wo)
     work = 54.0 * cin * cout * vox if cout > 1 else 4.0 * B * (cin * Di * Hi * Wi + Do * Ho * Wo)
-    with torch.cuda.device(x.device), _timed(lambda: conv3d_plan_name(a), work):
-        rc = _lib.load().dsm_conv3d_fwd(ctypes.byref(a), _stream())
-    _lib.check(rc, "dsm_conv3d_fwd")
-    del keep
+    _conv_launch(x, packed_weight, scale, shift, residual, y, B, cin, cout, (Di, Hi, Wi), (Do, Ho, Wo), res_size,
+                 stride, transposed, relu, work, virtual=virtual)
     return y
 
 
 def conv3d_plan_name(args):
     """Kernel variant ``dsm_conv3d_fwd`` picks for ``args`` (``dsm_conv3d_plan``)."""
-    buf = ctypes.create_string_buffer(96)
-    _lib.check(_lib.load().dsm_conv3d_plan(ctypes.byref(args), buf, 96), "dsm_conv3d_plan")
-    return buf.value.decode()
+    return _plan_name("dsm_conv3d_plan", args)
 
 
 # ----------------------------------------------------------------------------
 # host-side options, absolute maxima of the fp16 precisions, the virtual cost volume
 # ----------------------------------------------------------------------------
-import os as _os
-import weakref
-
 # host-side options (the library itself reads no environment variable): "conv_precision" starts from
 # DSM_CONV_PRECISION=bf16x3|fp32|f16x2|f16 so that scripts and the parity tests can switch whole runs
 _PRECISIONS = ("bf16x3", "fp32", "f16x2", "f16")
 
 
 def _env_precision():
-    v = _os.environ.get("DSM_CONV_PRECISION", "")
+    v = os.environ.get("DSM_CONV_PRECISION", "")
     if v and v not in _PRECISIONS:
         raise ValueError("DSM_CONV_PRECISION must be one of %s, got %r" % (_PRECISIONS, v))
     return v or "f16x2"
 
 
 def _env_flag(name, default):
-    v = _os.environ.get(name, "")
+    v = os.environ.get(name, "")
     if v not in ("", "0", "1"):
         raise ValueError("%s must be 0 or 1, got %r" % (name, v))
     return default if v == "" else v == "1"
@@ -523,10 +507,16 @@ def set_option(name, value):
     return old
 
 
-def _conv_flags():
+def _mode(mode):
+    """The precision mode a launch runs in: ``mode``, or (None) the ``conv_precision`` option.  A backward that
+    must match its forward passes the forward's; nothing swaps the option, which every thread reads."""
+    return _OPTIONS["conv_precision"] if mode is None else mode
+
+
+def _conv_flags(mode=None):
     """dsm_conv3d_args.flags of every convolution launch: precision "fp32" keeps the exact fp32-input
     MFMA kernels; ``conv_flags`` carries raw A/B bits (tile height, grid size: include/dsmnet_hip.h)."""
-    return (_lib.DSM_CONV_FP32_MFMA if _OPTIONS["conv_precision"] == "fp32" else 0) | _OPTIONS["conv_flags"]
+    return (_lib.DSM_CONV_FP32_MFMA if _mode(mode) == "fp32" else 0) | _OPTIONS["conv_flags"]
 
 
 def get_option(name):
@@ -632,8 +622,8 @@ class amax_scope(object):
         return False
 
 
-def needs_amax():
-    return _OPTIONS["conv_precision"] in ("f16x2", "f16")
+def needs_amax(mode=None):
+    return _mode(mode) in ("f16x2", "f16")
 
 
 def absmax(x):
@@ -718,11 +708,11 @@ def _split_kernel_layer(a):
     return a.stride == 1 or (kd == 3 and a.Cout == 64)
 
 
-def _set_precision(a, x, y):
+def _set_precision(a, x, y, mode=None):
     """precision / x_amax / y_amax of a ``dsm_conv3d_args``.  Returns the tensors the launch must
     keep alive.  ``x``, ``y``: the input and output tensors (NDHWC / NHWC memory); ``y`` None:
     the output needs no maximum (Cout = 1 heads)."""
-    mode = _OPTIONS["conv_precision"]
+    mode = _mode(mode)
     if mode not in ("f16x2", "f16"):
         return None
     a.precision = _lib.DSM_PREC_F16X2 if mode == "f16x2" else _lib.DSM_PREC_F16
@@ -736,6 +726,43 @@ def _set_precision(a, x, y):
         a.y_amax = ya.data_ptr()
         y._dsm_amax = ya
     return xa, ya
+
+
+def _conv_launch(x, packed_weight, scale, shift, residual, y, B, cin, cout, in_size, out_size, res_size, stride,
+                 transposed, relu, work, kd=0, k=0, dil=0, virtual=None, mode=None):
+    """The ``dsm_conv3d_fwd`` call of ``conv3d_block``, ``conv2d_block`` and ``conv2d_transposed_block``, which
+    have converted the layouts, worked out the extents and allocated ``y``.  ``in_size`` / ``out_size`` /
+    ``res_size``: (D, H, W) of ``x`` / ``y`` / ``residual`` (None without one); ``kd``, ``k``, ``dil``: 0 is the
+    struct's default (3 x 3 x 3 taps, dilation 1); ``virtual``: the ``VirtualVolume`` that ``x`` holds the
+    features of; ``work``: the launch's FLOPs or bytes for the timer; ``mode``: see ``_mode``."""
+    a = _lib.Conv3dArgs()
+    a.x, a.w_packed, a.y = _p(x), _p(packed_weight), _p(y)
+    a.scale, a.shift, a.residual = _p(scale), _p(shift), _p(residual)
+    a.B, a.Cin, a.Cout = B, cin, cout
+    a.Di, a.Hi, a.Wi = in_size
+    a.Do, a.Ho, a.Wo = out_size
+    if res_size is not None:
+        a.Dr, a.Hr, a.Wr = res_size
+    a.stride, a.transposed, a.relu = int(stride), int(transposed), int(relu)
+    a.kd, a.k, a.dil = int(kd), int(k), int(dil)
+    a.flags = _conv_flags(mode)
+    if virtual is not None:
+        a.vol_virtual, a.vol_mask_left = 1, int(virtual.mask_left)
+    keep = _set_precision(a, x, y if cout > 1 else None, mode)
+    lib = _lib.load()
+    ws = None
+    if kd == 1 and cout in WIDE2D_COUT:
+        # the wide layers' K-split partial sums: from torch's caching allocator, per call (no
+        # synchronisation; inside a hipGraph capture the block belongs to the graph's pool).  Asked for
+        # these layers only: the query runs the planner
+        nws = lib.dsm_conv3d_workspace_bytes(ctypes.byref(a))
+        if nws:
+            ws = torch.empty(nws // 4, device=y.device, dtype=torch.float32)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), nws
+    with torch.cuda.device(y.device), _timed(lambda: _plan_name("dsm_conv3d_plan", a), work):
+        rc = lib.dsm_conv3d_fwd(ctypes.byref(a), _stream())
+    _lib.check(rc, "dsm_conv3d_fwd")
+    del keep, ws                                     # alive until the call has returned
 
 
 class VirtualVolume(object):
@@ -853,7 +880,7 @@ def pack_conv2d_weight(weight, cin_padded=None):
 
 
 def conv2d_block(x, packed_weight, cout, scale=None, shift=None, residual=None, stride=1,
-                 relu=0, k=3, dilation=1):
+                 relu=0, k=3, dilation=1, mode=None):
     """y = relu?(conv2d(x) * scale + shift (+ residual)) on NHWC maps, "same" padding.
     ``x``: (B, Cin, H, W) in torch.channels_last memory, Cin a multiple of 16.  Inference only."""
     _require_device("conv2d_block", x, packed_weight, scale, shift, residual)
@@ -861,46 +888,20 @@ def conv2d_block(x, packed_weight, cout, scale=None, shift=None, residual=None, 
         x = carry_amax(x.contiguous(memory_format=_CL2D), x)
     B, cin, Hi, Wi = x.shape
     Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
-    a = _lib.Conv3dArgs()
     if residual is not None:
         if tuple(residual.shape) != (B, cout, Ho, Wo):
             raise ValueError("conv2d_block: residual shape %s != %s"
                              % (tuple(residual.shape), (B, cout, Ho, Wo)))
         if not residual.is_contiguous(memory_format=_CL2D):
             residual = residual.contiguous(memory_format=_CL2D)
-        a.Dr, a.Hr, a.Wr = 1, Ho, Wo
-    dev = packed_weight.device
-    y = torch.empty((B, cout, Ho, Wo), device=dev, dtype=torch.float32, memory_format=_CL2D)
-    a.x = x.data_ptr()
-    a.w_packed = packed_weight.data_ptr()
-    a.y = y.data_ptr()
-    a.scale = None if scale is None else scale.data_ptr()
-    a.shift = None if shift is None else shift.data_ptr()
-    a.residual = None if residual is None else residual.data_ptr()
-    a.B, a.Cin, a.Cout = B, cin, cout
-    a.Di, a.Hi, a.Wi = 1, Hi, Wi
-    a.Do, a.Ho, a.Wo = 1, Ho, Wo
-    a.stride, a.transposed, a.relu = int(stride), 0, int(relu)
-    a.kd, a.k, a.dil = 1, int(k), int(dilation)
-    a.flags = _conv_flags()
-    keep = _set_precision(a, x, y)
-    ws = None
-    if cout in WIDE2D_COUT:
-        # the wide layers' K-split partial sums: from torch's caching allocator, per call (no
-        # synchronisation; inside a hipGraph capture the block belongs to the graph's pool)
-        nws = _lib.load().dsm_conv3d_workspace_bytes(ctypes.byref(a))
-        if nws:
-            ws = torch.empty(nws // 4, device=dev, dtype=torch.float32)
-            a.workspace, a.workspace_bytes = ws.data_ptr(), nws
-    work = 2.0 * k * k * cin * cout * B * Ho * Wo
-    with torch.cuda.device(dev), _timed(lambda: conv3d_plan_name(a), work):
-        rc = _lib.load().dsm_conv3d_fwd(ctypes.byref(a), _stream())
-    _lib.check(rc, "dsm_conv3d_fwd")
-    del keep, ws
+    y = torch.empty((B, cout, Ho, Wo), device=packed_weight.device, dtype=torch.float32, memory_format=_CL2D)
+    _conv_launch(x, packed_weight, scale, shift, residual, y, B, cin, cout, (1, Hi, Wi), (1, Ho, Wo),
+                 None if residual is None else (1, Ho, Wo), stride, False, relu,
+                 2.0 * k * k * cin * cout * B * Ho * Wo, kd=1, k=k, dil=dilation, mode=mode)
     return y
 
 
-def conv2d_transposed_block(x, packed_weight, cout, out_size):
+def conv2d_transposed_block(x, packed_weight, cout, out_size, mode=None):
     """Backward-data of a stride-2 wide layer (plan kind 9 of ``dsm_conv3d_fwd``, the transposed mode of the
     wide kernel): ``conv_transpose2d(x, W, stride 2, padding 1, output_padding 1)[:, :, :Ho, :Wo]`` with
     ``packed_weight`` the pack of the flipped, in/out-transposed ``W`` and ``out_size`` = (Ho, Wo), the extent
@@ -914,30 +915,13 @@ def conv2d_transposed_block(x, packed_weight, cout, out_size):
     if not (2 * Hi - 1 <= Ho <= 2 * Hi and 2 * Wi - 1 <= Wo <= 2 * Wi):
         raise ValueError("conv2d_transposed_block: output %s is no stride-2 source of %s"
                          % ((Ho, Wo), (Hi, Wi)))
-    dev = packed_weight.device
-    y = torch.empty((B, cout, Ho, Wo), device=dev, dtype=torch.float32, memory_format=_CL2D)
-    a = _lib.Conv3dArgs()
-    a.x, a.w_packed, a.y = x.data_ptr(), packed_weight.data_ptr(), y.data_ptr()
-    a.B, a.Cin, a.Cout = B, cin, cout
-    a.Di, a.Hi, a.Wi = 1, Hi, Wi
-    a.Do, a.Ho, a.Wo = 1, Ho, Wo
-    a.stride, a.transposed, a.relu = 2, 1, 0
-    a.kd, a.k, a.dil = 1, 3, 1
-    a.flags = _conv_flags()
-    keep = _set_precision(a, x, y)
-    ws = None
-    nws = _lib.load().dsm_conv3d_workspace_bytes(ctypes.byref(a))
-    if nws:                                          # K-split partial sums, from torch's caching allocator
-        ws = torch.empty(nws // 4, device=dev, dtype=torch.float32)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), nws
-    with torch.cuda.device(dev), _timed(lambda: conv3d_plan_name(a), 18.0 * cin * cout * B * Ho * Wo):
-        rc = _lib.load().dsm_conv3d_fwd(ctypes.byref(a), _stream())
-    _lib.check(rc, "dsm_conv3d_fwd")
-    del keep, ws
+    y = torch.empty((B, cout, Ho, Wo), device=packed_weight.device, dtype=torch.float32, memory_format=_CL2D)
+    _conv_launch(x, packed_weight, None, None, None, y, B, cin, cout, (1, Hi, Wi), (1, Ho, Wo), None, 2, True, 0,
+                 18.0 * cin * cout * B * Ho * Wo, kd=1, k=3, dil=1, mode=mode)
     return y
 
 
-def bias_relu_bwd(gy, y, need_db=True):
+def bias_relu_bwd(gy, y, need_db=True, mode=None):
     """``g = where(y > 0, gy, 0)`` as a tensor of its own (``gy`` is never written), ``db = g.sum over pixels``
     in a fixed order (or None) and, in the fp16 modes, the maximum of ``|g|`` attached to ``g`` -- one pass,
     ``dsm_bias_relu_bwd`` (csrc/relu_bwd.hip).  ``gy``, ``y``: (B, C, H, W) channels_last, C % 4 == 0."""
@@ -954,7 +938,7 @@ def bias_relu_bwd(gy, y, need_db=True):
     if need_db:
         db = torch.empty(C, device=y.device, dtype=torch.float32)
         ws = torch.empty(min(512, (M + 7) // 8) * C, device=y.device, dtype=torch.float32)
-    if needs_amax():
+    if needs_amax(mode):
         ga = _ARENA.slot(y.device)
         g._dsm_amax = ga
     with torch.cuda.device(y.device), _timed("dsm_bias_relu_bwd", 0.0):
@@ -987,12 +971,9 @@ def basicblock2d(x, packed1, scale1, shift1, packed2, scale2, shift2, relu=False
         raise ValueError("basicblock2d: 32 or 64 channels and an fp16 precision mode, got C=%d, %s" % (C, mode))
     y = torch.empty((B, C, H, W), device=x.device, dtype=torch.float32, memory_format=_CL2D)
     a = _lib.BasicBlock2dArgs()
-    a.x, a.y = x.data_ptr(), y.data_ptr()
-    a.w1_packed, a.w2_packed = packed1.data_ptr(), packed2.data_ptr()
-    a.scale1 = None if scale1 is None else scale1.data_ptr()
-    a.shift1 = None if shift1 is None else shift1.data_ptr()
-    a.scale2 = None if scale2 is None else scale2.data_ptr()
-    a.shift2 = None if shift2 is None else shift2.data_ptr()
+    a.x, a.y = _p(x), _p(y)
+    a.w1_packed, a.w2_packed = _p(packed1), _p(packed2)
+    a.scale1, a.shift1, a.scale2, a.shift2 = _p(scale1), _p(shift1), _p(scale2), _p(shift2)
     a.B, a.H, a.W, a.C = B, H, W, C
     a.relu = 1 if relu else 0
     a.no_skip = 0 if skip else 1
@@ -1118,9 +1099,9 @@ def spp_head(raw, skip, w_t, scale, shift):
 # ----------------------------------------------------------------------------
 # Conv3d / ConvTranspose3d (k=3) with autograd: training through the 3-D trunk
 # ----------------------------------------------------------------------------
-def _wgrad_precision(x, g):
-    """(precision, x_amax, g_amax) of a weight-gradient launch under the current ``conv_precision``."""
-    mode = _OPTIONS["conv_precision"]
+def _wgrad_precision(x, g, mode=None):
+    """(precision, x_amax, g_amax) of a weight-gradient launch in ``mode`` (None: the ``conv_precision`` option)."""
+    mode = _mode(mode)
     if mode not in ("f16x2", "f16"):
         return _lib.DSM_PREC_F32, None, None
     return (_lib.DSM_PREC_F16X2 if mode == "f16x2" else _lib.DSM_PREC_F16), amax_of(x), amax_of(g)
@@ -1347,16 +1328,16 @@ def conv2d_variant(cout, stride, k, dilation):
     return cout in (32, 64, 128) and (stride, cout // 32, k, dilation) in _CONV2D_VARIANTS
 
 
-def _wgrad2d(x_cl, g_cl, stride, dilation, label="conv2d_wgrad_kernel"):
+def _wgrad2d(x_cl, g_cl, stride, dilation, label="conv2d_wgrad_kernel", mode=None):
     """dW[g][c][ky][kx] = sum_v X[v*stride + (k - 1)*dilation][c] G[v][g]  ->  (cg, cx, 3, 3)."""
     B, cx, Hx, Wx = x_cl.shape
     _, cg, Hg, Wg = g_cl.shape
     ws = torch.empty((cx // 32) * (cg // 32) * 9 * 1024, device=x_cl.device, dtype=torch.float32)
     dw = torch.empty((cg, cx, 3, 3), device=x_cl.device, dtype=torch.float32)
-    prec, xa, ga = _wgrad_precision(x_cl, g_cl)
+    prec, xa, ga = _wgrad_precision(x_cl, g_cl, mode)
     with torch.cuda.device(x_cl.device), _timed(label, 18.0 * cx * cg * B * Hg * Wg):
         rc = _lib.load().dsm_conv2d_wgrad(_p(x_cl), _p(g_cl), _p(ws), _p(dw), B, cx, cg, Hx, Wx,
-                                          Hg, Wg, int(stride), int(dilation), _conv_flags(), prec,
+                                          Hg, Wg, int(stride), int(dilation), _conv_flags(mode), prec,
                                           _p(xa), _p(ga), _stream())
     _lib.check(rc, "dsm_conv2d_wgrad")
     return dw
@@ -1431,7 +1412,6 @@ _WIDE_PACK_MISSES = {"forward": 0, "gradient": 0}      # packs made so far (test
 
 
 def _wide_pack_entry(weight):
-    from .blocks3d import _versions                    # (blocks3d imports this module)
     key = _versions(weight)
     ent = _WIDE_PACKS.get(id(weight))
     if ent is None or ent["ref"]() is not weight:
@@ -1486,32 +1466,24 @@ class WideConv2dReLUFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        mode = _OPTIONS["conv_precision"]
-        _OPTIONS["conv_precision"] = ctx.mode          # the mode the saved maxima and the forward belong to
-        try:
-            return WideConv2dReLUFunction._backward(ctx, gy)
-        finally:
-            _OPTIONS["conv_precision"] = mode
-
-    @staticmethod
-    def _backward(ctx, gy):
         x, weight, y = ctx.saved_tensors
+        mode = ctx.mode                                # the mode the saved maxima and the forward belong to
         for t, slot in zip((x, y), ctx.amax):
             if slot is not None and getattr(t, "_dsm_amax", None) is None:
                 t._dsm_amax = slot
         stride = ctx.stride
         cout, cin = weight.shape[0], weight.shape[1]
         need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
-        g, db = bias_relu_bwd(gy, y, need_db)
+        g, db = bias_relu_bwd(gy, y, need_db, mode=mode)
         dx = dw = None
         if need_dx:
             packed = _wide_pack(ctx.packs, weight, "gradient")
             if stride == 1:
-                dx = conv2d_block(g, packed, cin, stride=1)
+                dx = conv2d_block(g, packed, cin, stride=1, mode=mode)
             else:
-                dx = conv2d_transposed_block(g, packed, cin, x.shape[2:])
+                dx = conv2d_transposed_block(g, packed, cin, x.shape[2:], mode=mode)
         if need_dw:
-            dw = _wgrad2d(x, g, stride, 1, "conv2d_wgrad_kernel<S=%d,%dx%d>" % (stride, cin, cout))
+            dw = _wgrad2d(x, g, stride, 1, "conv2d_wgrad_kernel<S=%d,%dx%d>" % (stride, cin, cout), mode=mode)
         return dx, dw, db, None
 
 

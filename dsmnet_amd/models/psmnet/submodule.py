@@ -14,7 +14,8 @@ import torch.nn.functional as F
 from ... import blocks2d
 from ... import costvolume as cv
 from ...blocks2d import ConvBN2d, _Folded2d, run_conv2d, stage_image_nhwc16
-from ...blocks3d import ConvBN3d, _versions
+from ...blocks3d import ConvBN3d
+from ...folds import _versions, fold_affine
 
 # DSM_TRAIN_SPP=interp (read by this host module) keeps F.interpolate under autograd (A/B runs)
 _SPP_MATMUL = __import__("os").environ.get("DSM_TRAIN_SPP", "matmul") != "interp"
@@ -165,11 +166,9 @@ class feature_extraction(nn.Module):
         if getattr(self, "_spp_key", None) != key:
             with torch.no_grad():
                 w_t = torch.stack([c[0].weight.reshape(32, 128).t() for c in convs]).contiguous()
-                inv = [torch.rsqrt(c[1].running_var + c[1].eps) for c in convs]
-                scale = torch.stack([c[1].weight * i for c, i in zip(convs, inv)])
-                shift = torch.stack([c[1].bias - c[1].running_mean * s
-                                     for c, s in zip(convs, scale)])
-            self._spp_cache = (w_t, scale.contiguous(), shift.contiguous())
+                rows = [fold_affine(None, c[1], 32, c[0].weight.device) for c in convs]
+                scale, shift = (torch.stack(r) for r in zip(*rows))
+            self._spp_cache = (w_t, scale, shift)
             self._spp_key = key
         return self._spp_cache
 

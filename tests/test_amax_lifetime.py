@@ -194,3 +194,62 @@ def test_an_exception_inside_a_scope_closes_it(f16x2):
             with cv.amax_scope(CPU):
                 raise KeyError("x")
     assert cv._ARENA.depth[("cpu", None)] == 0
+
+
+def wide_layer_args():
+    """``dsm_conv3d_args`` of a wide 2-D layer (3x3, 256 -> 256 channels), which every fp16 mode runs on a split
+    kernel, with its input and output as CPU tensors."""
+    from dsmnet_amd import _lib
+    a = _lib.Conv3dArgs()
+    a.B, a.Cin, a.Cout = 1, 256, 256
+    a.Di, a.Hi, a.Wi = a.Do, a.Ho, a.Wo = 1, 4, 4
+    a.stride, a.kd, a.k, a.dil = 1, 1, 3, 1
+    return a, torch.full((1, 256, 4, 4), 3.0), torch.zeros(1, 256, 4, 4)
+
+
+def test_the_mode_of_a_launch_is_an_argument_not_the_option(passes):
+    """What ``WideConv2dReLUFunction.backward`` relies on: ``_set_precision``, ``_conv_flags``, ``_wgrad_precision``
+    and ``needs_amax`` (the slot of ``bias_relu_bwd``) follow the mode they are given, and the option -- which
+    other threads read -- is never written."""
+    from dsmnet_amd import _lib
+    with precision("bf16x3"):
+        with cv.amax_scope(CPU):                                                # no fp16 mode: opens nothing
+            a, x, y = wide_layer_args()
+            keep = cv._set_precision(a, x, y, mode="f16x2")
+            assert a.precision == _lib.DSM_PREC_F16X2 and a.x_amax and a.y_amax
+            assert y._dsm_amax is keep[1] and a.y_amax == keep[1].data_ptr()
+            assert a.x_amax == keep[0].data_ptr() and keep[0].item() == 3.0 and [id(t) for t in passes] == [id(x)]
+            assert cv.needs_amax("f16") and not cv.needs_amax()
+            g = torch.full((1, 256, 4, 4), 0.5)
+            prec, xa, ga = cv._wgrad_precision(x, g, mode="f16")
+            assert prec == _lib.DSM_PREC_F16 and xa is keep[0] and ga.item() == 0.5
+            assert cv.get_option("conv_precision") == "bf16x3"
+    with precision("fp32"):
+        assert cv._conv_flags() & _lib.DSM_CONV_FP32_MFMA
+        assert not cv._conv_flags(mode="f16x2") & _lib.DSM_CONV_FP32_MFMA
+        assert cv.get_option("conv_precision") == "fp32"
+    with precision("f16"):
+        assert cv._conv_flags(mode="fp32") & _lib.DSM_CONV_FP32_MFMA and not cv._conv_flags()
+        assert cv.get_option("conv_precision") == "f16"
+
+
+@pytest.mark.parametrize("option", ["bf16x3", "fp32", "f16x2", "f16"])
+def test_without_a_mode_every_launch_follows_the_option(option, passes):
+    from dsmnet_amd import _lib
+    want = {"f16x2": _lib.DSM_PREC_F16X2, "f16": _lib.DSM_PREC_F16}.get(option, _lib.DSM_PREC_F32)
+    with precision(option), cv.amax_scope(CPU):
+        a, x, y = wide_layer_args()
+        g = torch.full((1, 256, 4, 4), 0.5)
+        for mode in ({}, {"mode": None}):
+            keep = cv._set_precision(a, x, y, **mode)
+            prec, xa, ga = cv._wgrad_precision(x, g, **mode)
+            flags = cv._conv_flags(**mode)
+            assert a.precision == want and prec == want
+            assert bool(flags & _lib.DSM_CONV_FP32_MFMA) == (option == "fp32")
+            if want == _lib.DSM_PREC_F32:
+                assert keep is None and xa is None and ga is None and not a.x_amax and not a.y_amax
+                assert getattr(y, "_dsm_amax", None) is None and passes == []
+            else:
+                assert a.x_amax == keep[0].data_ptr() and a.y_amax == y._dsm_amax.data_ptr()
+                assert xa is keep[0] and ga.item() == 0.5
+        assert cv.needs_amax() == cv.needs_amax(None) == (want != _lib.DSM_PREC_F32)

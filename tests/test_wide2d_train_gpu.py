@@ -244,8 +244,10 @@ def test_backward_after_the_arena_began_again(cv, key, mode):
     check_gradients(key, mode, y.detach(), (xg.grad, wg.grad, bg.grad), tag=" (stale slots)")
 
 
-def test_backward_runs_in_the_mode_of_its_forward(cv):
-    """``conv_precision`` switched between forward and backward: the backward keeps the forward's mode."""
+@pytest.mark.parametrize("switched", ["bf16x3", "fp32"])
+def test_backward_runs_in_the_mode_of_its_forward(cv, switched):
+    """``conv_precision`` switched between forward and backward: the backward keeps the forward's mode, which it
+    hands to its launches (under "fp32" a launch that read the option would ask for the fp32-input MFMA)."""
     key = "B"
     x, w, b, pre, cot = T.case_data(key)
     with options(cv, conv_precision="f16x2"):
@@ -253,11 +255,11 @@ def test_backward_runs_in_the_mode_of_its_forward(cv):
         wg, bg = w.cuda().requires_grad_(True), b.cuda().requires_grad_(True)
         with cv.amax_scope(dev()):
             y = cv.wide_conv2d_relu(xg, wg, bg, T.CASES[key][2])
-            with options(cv, conv_precision="bf16x3"):
+            with options(cv, conv_precision=switched):
                 y.backward(cl(cot))
-                assert cv.get_option("conv_precision") == "bf16x3"
+                assert cv.get_option("conv_precision") == switched
         torch.cuda.synchronize()
-    check_gradients(key, "f16x2", y.detach(), (xg.grad, wg.grad, bg.grad), tag=" (mode switched)")
+    check_gradients(key, "f16x2", y.detach(), (xg.grad, wg.grad, bg.grad), tag=" (mode switched to %s)" % switched)
 
 
 # ------------------------------------------------------------------------------------------- 4. chain --
