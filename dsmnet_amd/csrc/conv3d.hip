@@ -1103,8 +1103,11 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
     *pl = Plan{1, 2, NT, 1, 16, 3, 3, 1};   // (32-channel chunks measured slower: 306 vs 283 us)
     return DSM_OK;
   }
+  // 32-bit offsets per input plane, the out-of-range marker (2^31) past its descriptor: a virtual volume's
+  // right half is staged through a descriptor of one feature plane plus the plane's shift, up to Di - 1 voxels
   if (a->stride == 1 && zs_layer(a->Cin, a->Cout, kd, k, 0) && bf16x3_enabled(a) &&
-      (unsigned long)a->Hi * a->Wi * a->Cin * (a->vol_virtual ? 2ul : 4ul) < 0x7fffffffUL) {   // 32-bit offsets per input plane
+      (a->vol_virtual ? ((unsigned long)a->Hi * a->Wi + a->Di - 1) * a->Cin * 2ul
+                      : (unsigned long)a->Hi * a->Wi * a->Cin * 4ul) < 0x7fffffffUL) {
     if (a->vol_virtual) DSM_REQUIRE(a->Cin % 64 == 0, DSM_ERR_UNSUPPORTED);   // [left | right], 32-channel groups each
     *pl = Plan{7, 1, 1, 2, 32, 3, 3, 1};
     return DSM_OK;
