@@ -21,6 +21,8 @@ DSM_CONV_NO_NSPLIT = 4
 DSM_CONV_NO_ONCE = 8
 DSM_CONV_KSPLIT_SHIFT = 8
 DSM_PREC_F32, DSM_PREC_F16, DSM_PREC_F16X2 = 0, 1, 2
+DSM_SIM_DOT, DSM_SIM_COSINE = 0, 1
+DSM_CORR_BWD_NAIVE = 1
 
 
 class Bn3dArgs(ctypes.Structure):
@@ -97,6 +99,11 @@ SIGNATURES = {
     "dsm_soft_argmin_fwd": (c_int, [c_void_p] * 3 + [c_int] * 10 + [c_void_p]),
     "dsm_soft_argmin_bwd": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
     "dsm_corr1d_plan": (c_int, [c_void_p] * 4 + [c_int] * 8 + [ctypes.c_char_p, c_int]),
+    "dsm_corr1d_sim_fwd": (c_int, [c_void_p] * 5 + [c_int] * 8 + [ctypes.c_float, c_int, c_void_p]),
+    "dsm_corr1d_sim_fwd_plan": (c_int, [c_void_p] * 5 + [c_int] * 8 + [ctypes.c_float, c_int, ctypes.c_char_p, c_int]),
+    "dsm_corr1d_sim_bwd": (c_int, [c_void_p] * 8 + [c_int] * 8 + [ctypes.c_float, c_int, c_int, c_void_p]),
+    "dsm_corr1d_sim_bwd_plan": (c_int, [c_void_p] * 8 + [c_int] * 8 + [ctypes.c_float, c_int, c_int, ctypes.c_char_p, c_int]),
+    "dsm_corr1d_sim_workspace_bytes": (c_size_t, [c_int] * 7),
     "dsm_concat_volume_fwd_plan": (c_int, [c_void_p] * 3 + [c_int] * 8 + [ctypes.c_char_p, c_int]),
     "dsm_concat_volume_bwd_plan": (c_int, [c_void_p] * 3 + [c_int] * 8 + [ctypes.c_char_p, c_int]),
     "dsm_soft_argmin_fwd_plan": (c_int, [c_void_p] * 3 + [c_int] * 10 + [ctypes.c_char_p, c_int]),

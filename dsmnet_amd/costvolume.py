@@ -177,6 +177,9 @@ class Corr1dFunction(torch.autograd.Function):
         D, stride, kernel_size = ctx.cfg
         g = grad_out.contiguous()
         B, C, H, W = fL.shape
+        if _OPTIONS["corr1d_tiled_bwd"]:
+            dfL, dfR = _corr1d_sim_bwd(g, fL, fR, None, None, D, stride, kernel_size, _lib.DSM_SIM_DOT, 0.0)
+            return dfL, dfR, None, None, None
         dfL, dfR = torch.empty_like(fL), torch.empty_like(fR)
         tmp = torch.empty_like(g) if kernel_size > 1 else None
         lib = _lib.load()
@@ -187,9 +190,84 @@ class Corr1dFunction(torch.autograd.Function):
         return dfL, dfR, None, None, None
 
 
-def corr1d(fL, fR, D, stride=1, kernel_size=1):
-    """``Corr1d(kernel_size, stride, D).forward(fL, fR)`` -> (B, D, H, W)."""
-    return Corr1dFunction.apply(fL, fR, int(D), int(stride), int(kernel_size))
+_SIMS = {"dot": _lib.DSM_SIM_DOT, "cosine": _lib.DSM_SIM_COSINE}
+
+
+def corr1d_sim_fwd_plan_name(fL, fR, out, raw, inv, B, C, H, W, D, stride=1, kernel_size=1, sim="cosine", eps=1e-8):
+    """Kernels ``dsm_corr1d_sim_fwd`` picks (``dsm_corr1d_sim_fwd_plan``): the names of ``corr1d_plan_name``,
+    with the prefix ``cos:`` for the cosine similarity."""
+    return _plan_name("dsm_corr1d_sim_fwd_plan", fL, fR, out, raw, inv, B, C, H, W, D, stride, kernel_size,
+                      _SIMS[sim], ctypes.c_float(eps), _lib.DSM_F32)
+
+
+def corr1d_sim_bwd_plan_name(grad_out, fL, fR, raw, inv, dfL, dfR, workspace, B, C, H, W, D, stride=1,
+                             kernel_size=1, sim="cosine", eps=1e-8, flags=0):
+    """Kernels ``dsm_corr1d_sim_bwd`` picks (``dsm_corr1d_sim_bwd_plan``): ``bwd_tile<S>`` or ``bwd_naive``,
+    behind ``prep+`` (cosine) and ``box3+`` / ``box+`` (kernel_size > 1)."""
+    return _plan_name("dsm_corr1d_sim_bwd_plan", grad_out, fL, fR, raw, inv, dfL, dfR, workspace, B, C, H, W, D,
+                      stride, kernel_size, _SIMS[sim], ctypes.c_float(eps), int(flags), _lib.DSM_F32)
+
+
+def _corr1d_sim_bwd(g, fL, fR, raw, inv, D, stride, kernel_size, sim, eps, flags=0):
+    """``dsm_corr1d_sim_bwd``: the tiled data gradient wherever its plan admits it (``flags``: DSM_CORR_BWD_NAIVE
+    forces the naive kernel).  No host read, no synchronisation."""
+    B, C, H, W = fL.shape
+    lib = _lib.load()
+    dfL, dfR = torch.empty_like(fL), torch.empty_like(fR)
+    nbytes = lib.dsm_corr1d_sim_workspace_bytes(B, C, H, W, D, kernel_size, sim)
+    ws = torch.empty(nbytes // 4, device=fL.device, dtype=torch.float32) if nbytes else None
+    with torch.cuda.device(fL.device), _timed("corr1d_bwd_kernel", 4.0 * (4 * B * C * H * W + B * D * H * W)):
+        rc = lib.dsm_corr1d_sim_bwd(_p(g), _p(fL), _p(fR), _p(raw), _p(inv), _p(dfL), _p(dfR), _p(ws), B, C, H, W,
+                                    D, stride, kernel_size, sim, eps, flags, _lib.DSM_F32, _stream())
+    _lib.check(rc, "dsm_corr1d_sim_bwd")
+    return dfL, dfR
+
+
+class Corr1dCosineFunction(torch.autograd.Function):
+    """``Corr1d(simfun=nn.CosineSimilarity(dim=1, eps))``: ``dsm_corr1d_sim_fwd`` / ``_bwd`` with DSM_SIM_COSINE
+    (include/dsmnet_hip.h has the formula and its gradients).  Saves the features, the inverse norms and the raw
+    (unfiltered) map; capturable in a graph."""
+
+    @staticmethod
+    def forward(ctx, fL, fR, D, stride, kernel_size, eps):
+        _require_device("corr1d", fL, fR)
+        if fL.dim() != 4:
+            raise ValueError("corr1d: expected (B,C,H,W) features, got %d-D" % fL.dim())
+        _same_shape("corr1d", fL, fR)
+        if kernel_size % 2 != 1:
+            raise AssertionError("kernel_size must be odd")      # util_conv.py:83
+        fL, fR = fL.contiguous(), fR.contiguous()
+        B, C, H, W = fL.shape
+        out = torch.empty((B, D, H, W), device=fL.device, dtype=fL.dtype)
+        raw = torch.empty_like(out) if kernel_size > 1 else None
+        inv = torch.empty((2, B, H, W), device=fL.device, dtype=fL.dtype)
+        lib = _lib.load()
+        with torch.cuda.device(fL.device), _timed("corr1d_cosine_fwd_kernel", 4.0 * (4 * B * C * H * W + B * D * H * W)):
+            rc = lib.dsm_corr1d_sim_fwd(_p(fL), _p(fR), _p(out), _p(raw), _p(inv), B, C, H, W, D, stride,
+                                        kernel_size, _lib.DSM_SIM_COSINE, eps, _lib.DSM_F32, _stream())
+        _lib.check(rc, "dsm_corr1d_sim_fwd")
+        ctx.save_for_backward(fL, fR, inv, out if raw is None else raw)
+        ctx.cfg = (D, stride, kernel_size, eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        fL, fR, inv, raw = ctx.saved_tensors
+        D, stride, kernel_size, eps = ctx.cfg
+        dfL, dfR = _corr1d_sim_bwd(grad_out.contiguous(), fL, fR, raw, inv, D, stride, kernel_size,
+                                   _lib.DSM_SIM_COSINE, eps)
+        return dfL, dfR, None, None, None, None
+
+
+def corr1d(fL, fR, D, stride=1, kernel_size=1, sim="dot", eps=1e-8):
+    """``Corr1d(kernel_size, stride, D, simfun).forward(fL, fR)`` -> (B, D, H, W).  ``sim``: "dot" (the
+    reference's default similarity) or "cosine" (``nn.CosineSimilarity(dim=1, eps)``: each norm clamped at
+    ``eps`` on its own, a clamped norm constant in the gradient)."""
+    if sim == "dot":
+        return Corr1dFunction.apply(fL, fR, int(D), int(stride), int(kernel_size))
+    if sim != "cosine":
+        raise ValueError("corr1d: sim must be 'dot' or 'cosine', got %r" % (sim,))
+    return Corr1dCosineFunction.apply(fL, fR, int(D), int(stride), int(kernel_size), float(eps))
 
 
 # ----------------------------------------------------------------------------
@@ -457,7 +535,8 @@ _OPTIONS = {"fuse_volume": True, "fuse_blocks": True, "conv_precision": _env_pre
             "wide_conv2d": _env_flag("DSM_WIDE_CONV2D", _WIDE_CONV2D_DEFAULT),
             "wide_conv2d_train": _env_flag("DSM_WIDE_CONV2D_TRAIN", False),
             "warp_train": _env_flag("DSM_WARP_TRAIN", False),
-            "decoder_train": _env_flag("DSM_DECODER_TRAIN", False)}
+            "decoder_train": _env_flag("DSM_DECODER_TRAIN", False),
+            "corr1d_tiled_bwd": False}
 
 
 def set_option(name, value):
@@ -490,6 +569,9 @@ def set_option(name, value):
     ``decoder_train`` -- ``decoder_level`` keeps its one-launch bias + ReLU + upsampling + concatenation under
     autograd (``DecoderCatFunction``, csrc/decoder.hip forward and backward); independent of ``warp_train``;
     default off (profiles/train_ops.md), starts from DSM_DECODER_TRAIN=0|1;
+    ``corr1d_tiled_bwd`` -- the backward of the dot-product ``corr1d`` goes through ``dsm_corr1d_sim_bwd`` (the
+    LDS-tiled data gradient where its plan admits it) instead of ``dsm_corr1d_bwd``; default off
+    (profiles/corr1d_sim.md).  The cosine similarity always takes that entry point;
     ``conv_flags`` -- raw dsm_conv3d_args.flags bits (tile height, grid size, K-ranges of the wide layers)."""
     if name == "conv_fp32":
         old = _OPTIONS["conv_precision"] == "fp32"

@@ -31,20 +31,33 @@ activefun_default = _default_act()
 class Corr1d(nn.Module):
     """``Corr1d(kernel_size, stride, D, simfun)``: plane ``i`` is the channel dot product of
     ``fL[..., x]`` with ``fR[..., x - i*stride]`` (zero for ``x < i*stride``), optionally box
-    filtered.  Only the default similarity is implemented on the device."""
+    filtered.  ``simfun``: None (the dot product, what the four models use) or an
+    ``nn.CosineSimilarity`` with ``dim == 1`` (the alternative util_conv.py:65 names): every product is
+    then divided by ``max(|fL[..., x]|, eps) * max(|fR[..., x - i*stride]|, eps)`` with the module's ``eps``,
+    each norm clamped on its own as ``F.cosine_similarity`` of torch >= 1.12 does (PyTorch 0.3 clamped the
+    product of the norms; the two differ only for feature vectors shorter than ``eps``), and a clamped norm is
+    a constant in the gradient.  Both run on the HIP kernels (csrc/corr1d.hip); any other callable raises
+    ``NotImplementedError``."""
 
     def __init__(self, kernel_size=1, stride=1, D=1, simfun=None):
         super(Corr1d, self).__init__()
-        if simfun is not None:
-            raise NotImplementedError("Corr1d on the MI355X path supports the default "
-                                      "dot-product similarity only (util_conv.py:68-69)")
+        if simfun is None:
+            self.sim, self.eps = "dot", 1e-8
+        elif isinstance(simfun, nn.CosineSimilarity) and simfun.dim == 1:
+            self.sim, self.eps = "cosine", float(simfun.eps)
+        else:
+            raise NotImplementedError("Corr1d on the MI355X path supports the default dot-product similarity "
+                                      "(util_conv.py:68-69) and nn.CosineSimilarity(dim=1) only")
         self.kernel_size, self.stride, self.D = kernel_size, stride, D
 
     def forward(self, fL, fR):
-        return cv.corr1d(fL, fR, self.D, self.stride, self.kernel_size)
+        if self.sim == "dot":
+            return cv.corr1d(fL, fR, self.D, self.stride, self.kernel_size)
+        return cv.corr1d(fL, fR, self.D, self.stride, self.kernel_size, sim=self.sim, eps=self.eps)
 
     def extra_repr(self):
-        return "kernel_size=%d, stride=%d, D=%d" % (self.kernel_size, self.stride, self.D)
+        s = "kernel_size=%d, stride=%d, D=%d" % (self.kernel_size, self.stride, self.D)
+        return s if self.sim == "dot" else s + ", simfun=CosineSimilarity(dim=1, eps=%g)" % self.eps
 
 
 class Conv2dReLU(nn.Sequential):

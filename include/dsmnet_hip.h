@@ -85,6 +85,56 @@ int dsm_corr1d_bwd(const void* grad_out, const void* fL, const void* fR,
                    int B, int C, int H, int W, int D, int stride, int ksize,
                    int dtype, dsm_stream_t stream);
 
+/* (ABI v7, additive) Corr1d with a similarity argument (the `simfun` of util_conv.py:57-66) and the tiled
+ * data gradient.  dsm_corr1d_fwd / _bwd / _plan above are unchanged; DSM_SIM_DOT here runs their kernels.
+ *
+ * DSM_SIM_COSINE is nn.CosineSimilarity(dim=1, eps) per plane, each norm clamped on its own
+ * (F.cosine_similarity of torch >= 1.12; PyTorch 0.3 clamped the product of the two norms):
+ *   a(b,y,x) = 1 / max(||fL[b,:,y,x]||, eps),   r(b,y,x) = 1 / max(||fR[b,:,y,x]||, eps),   x' = x - i*stride
+ *   raw[b,i,y,x] = a(x) r(x') sum_c fL[b,c,y,x] fR[b,c,y,x']      (x' >= 0, else 0)
+ *   out = raw (ksize 1) or the box filter of raw (ksize > 1), as for the dot product.
+ * Gradients are those of this formula with a clamped norm held constant: with g = box(grad_out) and
+ * g'_i(x) = g_i(x) a(x) r(x'),
+ *   dfL[c,x ] = sum_i g'_i(x)          fR[c,x - i s]   - [||fL(x)|| >= eps]  a(x)^2  fL[c,x]  sum_i g_i(x) raw_i(x)
+ *   dfR[c,x'] = sum_i g'_i(x' + i s)   fL[c,x' + i s]  - [||fR(x')|| >= eps] r(x')^2 fR[c,x'] sum_i g_i(x'+i s) raw_i(x'+i s)
+ * i.e. the dot-product backward applied to g', one pass in front and one term in the epilogue.
+ *
+ * Forward.  raw: (B,D,H,W), needed iff ksize > 1 (the unfiltered map; the cosine backward reads it).
+ * inv: (2,B,H,W) floats, needed iff DSM_SIM_COSINE, written here: a, then r.  eps > 0 (ignored for the dot
+ * product).  Cosine: 2 launches (ksize 1) or 3; no pass over the (B,D,H,W) map is added.
+ * Extents the cosine passes cannot index (B*H*W or W + D*stride above 2^31 - 1) are DSM_ERR_UNSUPPORTED.
+ * Plan names: those of dsm_corr1d_plan, cosine with the prefix "cos:" ("cos:tile<1,1>+box3"); inv counts
+ * among the pointers that 16-byte accesses need aligned. */
+enum dsm_corr_sim { DSM_SIM_DOT = 0, DSM_SIM_COSINE = 1 };
+
+int dsm_corr1d_sim_fwd(const void* fL, const void* fR, void* out, void* raw, void* inv,
+                       int B, int C, int H, int W, int D, int stride, int ksize,
+                       int sim, float eps, int dtype, dsm_stream_t stream);
+int dsm_corr1d_sim_fwd_plan(const void* fL, const void* fR, const void* out, const void* raw,
+                            const void* inv, int B, int C, int H, int W, int D, int stride, int ksize,
+                            int sim, float eps, int dtype, char* buf, int len);
+
+/* Backward.  raw_or_out: the forward's raw map (ksize > 1) or its out (ksize 1), and inv: the forward's;
+ * both needed iff DSM_SIM_COSINE.  dfL, dfR: (B,C,H,W), fully overwritten.  workspace: at least
+ * dsm_corr1d_sim_workspace_bytes(...) bytes, needed iff that is not 0.
+ * flags: DSM_CORR_BWD_NAIVE forces the one-thread-per-element kernel of dsm_corr1d_bwd (A/B runs).
+ * Plan names: "bwd_tile<S>" (S = stride 1 | 2; needs W % 4 == 0, D <= 96, at most 150 KB of LDS and fL, fR,
+ * dfL, dfR, the gradient it reads -- grad_out, or the workspace when ksize > 1 or cosine -- 16-byte aligned)
+ * or "bwd_naive"; in front "prep+" (cosine: g' and the two sums) and before that "box3+" (ksize 3, W % 4 == 0,
+ * grad_out and workspace 16-byte aligned) or "box+" (any other ksize > 1).  No atomics anywhere: results
+ * are bit-reproducible. */
+#define DSM_CORR_BWD_NAIVE 1
+
+int dsm_corr1d_sim_bwd(const void* grad_out, const void* fL, const void* fR,
+                       const void* raw_or_out, const void* inv, void* dfL, void* dfR, void* workspace,
+                       int B, int C, int H, int W, int D, int stride, int ksize,
+                       int sim, float eps, int flags, int dtype, dsm_stream_t stream);
+int dsm_corr1d_sim_bwd_plan(const void* grad_out, const void* fL, const void* fR,
+                            const void* raw_or_out, const void* inv, const void* dfL, const void* dfR,
+                            const void* workspace, int B, int C, int H, int W, int D, int stride, int ksize,
+                            int sim, float eps, int flags, int dtype, char* buf, int len);
+size_t dsm_corr1d_sim_workspace_bytes(int B, int C, int H, int W, int D, int ksize, int sim);
+
 /* ---------------------------------------------------------------------------
  * (a2,a3) concatenation cost volume.  Replaces the inline loops of
  * models/gcnet.py:130-135 (mask_left = 0) and
