@@ -79,10 +79,11 @@ __global__ __launch_bounds__(512, (BbCfg<PM, C>::WGS)) void basicblock2d_kernel(
   const int ty0 = (id % p.nty) * TY;
   const int b = id / p.nty;
 
-  // power-of-two factors: x and the two weight tensors (conv_split.hpp); the intermediate's comes later
-  const int ex = dsm_amax_exponent(*p.x_amax), ew1 = dsm_amax_exponent(*p.w1_amax), ew2 = dsm_amax_exponent(*p.w2_amax);
-  const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, dsm_pow2f(ex))));
-  const float so1 = dsm_pow2f(-(ex + ew1));
+  // power-of-two factors: x and the two weight tensors (split_core.hpp); the intermediate's comes later,
+  // per tile, and pairs with the second weight tensor's exponent there
+  const SplitScale ss = split_scale<PM>(p.x_amax, p.w1_amax);
+  const float sx = ss.sx, so1 = ss.out;
+  const int ew2 = dsm_amax_exponent(*p.w2_amax);
   if (tid < 4 * C) {
     const int c = tid % C, which = tid / C;
     const float* src = which == 0 ? p.scale1 : which == 1 ? p.shift1 : which == 2 ? p.scale2 : p.shift2;
@@ -285,7 +286,7 @@ __global__ __launch_bounds__(512, (BbCfg<PM, C>::WGS)) void basicblock2d_kernel(
         store_tile<C>(acc2[m], af, p.relu, p.y + (((long)b * p.H + yo) * p.W + xo) * C + 32 * nw + 4 * h, rr[m], p.skip != 0, am);
     }
   }
-  flush_amax8(p.y_amax, am, red + 8);
+  publish_amax<8>(p.y_amax, am, red + 8);
 }
 
 template <int PM, int C>
@@ -295,12 +296,7 @@ int launch_basicblock2d(BbParams p, hipStream_t s) {
   const long nt = (long)p.B * p.nty * p.ntx;
   if (nt >= (1L << 30)) return DSM_ERR_UNSUPPORTED;
   p.ntiles = (int)nt;
-  static thread_local bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute((const void*)basicblock2d_kernel<PM, C>, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS) != hipSuccess)
-      return DSM_ERR_LAUNCH;
-    configured = true;
-  }
+  DSM_REQUIRE((dsm_allow_lds<basicblock2d_kernel<PM, C>>(Cf::LDS) == DSM_OK), DSM_ERR_LAUNCH);
   hipLaunchKernelGGL((basicblock2d_kernel<PM, C>), dim3((unsigned)nt), dim3(Cf::THREADS), Cf::LDS, s, p);
   return dsm_launch_status();
 }

@@ -9,7 +9,7 @@
 //             out = relu?( y*scale + shift (+ residual, cropped to the common corner) )
 //   backward: bn_bwd_reduce (sum g', sum g' xhat) -> bn_bwd_apply (dy, dresidual); dgamma, dbeta
 // All HBM-bound streaming passes: 16 bytes per lane, channels innermost.
-#include "common.hpp"
+#include "split_core.hpp"    // track_amax, publish_amax_per_wave
 
 namespace {
 
@@ -94,21 +94,9 @@ __device__ __forceinline__ int quad_of(long i, int nq) {
   return (nq & (nq - 1)) == 0 ? (int)(i & (nq - 1)) : (int)(i % nq);
 }
 
-// max |v| of a launch's output for the fp16 convolution modes (include/dsmnet_hip.h: x_amax): a wave
-// reduction, then one atomic per wave -- and none once the slot holds as much (the blocks of an
-// element-wise pass are many; most of them find the maximum already there)
-__device__ __forceinline__ float amax4(float am, const f32x4 v) {
-  return fmaxf(fmaxf(am, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-}
-// (the apply kernels walk their elements with a bounded grid, so a launch issues at most a few
-// thousand of these: same-address atomics serialise in L2 at ~5 ns each)
-__device__ __forceinline__ void wave_amax(float* slot, float am) {
-  if (!slot) return;
-#pragma unroll
-  for (int o = 32; o; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
-  if ((threadIdx.x & 63) == 0 && am > *reinterpret_cast<volatile float*>(slot))
-    atomicMax(reinterpret_cast<unsigned*>(slot), __builtin_bit_cast(unsigned, am));
-}
+// max |v| of a launch's output for the fp16 convolution modes (include/dsmnet_hip.h: x_amax): track_amax per
+// quad, then publish_amax_per_wave (split_core.hpp) -- the apply kernels walk their elements with a bounded
+// grid, which bounds the atomics of a launch
 constexpr int BN_APPLY_MAX_BLOCKS = 4096;
 
 // out[b,z,y,x,:] = relu?( y*scale + shift (+ res) ) over the common corner; thread = (out voxel, quad)
@@ -139,9 +127,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   if (res) t += *reinterpret_cast<const f32x4*>(res + vr * d.C + 4 * q);
   if (relu == 1) t = relu4(t);
   *reinterpret_cast<f32x4*>(out + i * 4) = t;
-  am = amax4(am, t);
+  track_amax(am, t);
   }
-  wave_amax(out_amax, am);
+  publish_amax_per_wave(out_amax, am);
 }
 
 // g' = g masked by the ReLU; per channel sum g' and sum g'*xhat over the output corner
@@ -235,17 +223,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     const f32x4 xhat = (yv - mean) * istd;
     const f32x4 dyv = sc * (gv - mg - xhat * mgx);
     *reinterpret_cast<f32x4*>(dy + vy * d.C + 4 * q) = dyv;
-    amy = amax4(amy, dyv);
+    track_amax(amy, dyv);
   }
   if (in_r) {
     const long vr = vr_;
     const f32x4 drv = relu == 2 ? graw : gv;
     *reinterpret_cast<f32x4*>(dres + vr * d.C + 4 * q) = drv;
-    amr = amax4(amr, drv);
+    track_amax(amr, drv);
   }
   }
-  wave_amax(dy_amax, amy);
-  wave_amax(dres_amax, amr);
+  publish_amax_per_wave(dy_amax, amy);
+  publish_amax_per_wave(dres_amax, amr);
 }
 
 int check_bn(const dsm_bn3d_args* a) {

@@ -5,6 +5,7 @@
 The library is built in-tree (next to the sources) so that it travels with the
 repository snapshot; it is git-ignored (*.so).
 """
+import glob
 import os
 import subprocess
 import sys
@@ -38,9 +39,8 @@ def build(force=False, verbose=True, stamps=False):
         print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
         return lib
-    hdrs = [os.path.join(HERE, "common.hpp"), os.path.join(HERE, "conv_split.hpp"), os.path.join(HERE, "conv_zs.hpp"), os.path.join(HERE, "deconv_zs.hpp"), os.path.join(HERE, "conv_common.hpp"),
-            os.path.join(HERE, "basicblock2d.hpp"), os.path.join(HERE, "conv_wide2d.hpp"),
-            os.path.join(HERE, "..", "..", "include", "dsmnet_hip.h")]
+    # every header of this directory and the C ABI: a new header cannot be forgotten
+    hdrs = sorted(glob.glob(os.path.join(HERE, "*.hpp"))) + [os.path.join(HERE, "..", "..", "include", "dsmnet_hip.h")]
     srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
     objs = []
     jobs = []

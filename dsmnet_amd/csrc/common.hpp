@@ -30,3 +30,32 @@ static inline bool dsm_aligned16(const void* p) { return (((uintptr_t)p) & 15u) 
 static inline int dsm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 #define DSM_REQUIRE(cond, code) do { if (!(cond)) return (code); } while (0)
+
+// Make sure `kernel` may use `bytes` of dynamic LDS (past 64 KiB a kernel's limit has to be raised before
+// its first launch).  The flag -- one per kernel and host thread -- is the only state the library keeps
+// (DESIGN.md 1): a launch after the first pays one thread-local load.  Only the FIRST call's `bytes` reaches
+// the runtime, and nothing here checks later ones against it: every caller passes a size that is fixed per
+// kernel instantiation (a compile-time constant, or the most any of its plans may ask for).
+template <auto kernel>
+static inline int dsm_allow_lds(size_t bytes) {
+  static thread_local bool configured = false;
+  if (!configured) {
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+      return DSM_ERR_LAUNCH;
+    configured = true;
+  }
+  return DSM_OK;
+}
+
+// torch.linspace(start, end, steps)[i], evaluated as torch does (from the nearer end)
+__device__ __forceinline__ float linspace_at(float start, float end, int steps, int i) {
+  const float step = (end - start) / (float)(steps - 1);
+  return i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - i - 1);
+}
+
+// sum over the wave's 64 lanes, in every lane (xor butterfly)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}

@@ -323,7 +323,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3d_mfma_kernel(ConvParams p) 
     ck = nck; t = nt_;
     if (t >= end) break;
   }
-  flush_amax(p.y_amax, am, reinterpret_cast<float*>(tile));
+  publish_amax<4>(p.y_amax, am, reinterpret_cast<float*>(tile));
 }
 
 #include "conv_split.hpp"   // conv_split_kernel, deconv_split_kernel, pack_weights_split_kernel
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void deconv3d_mfma_kernel(ConvParams p
     ck = nck; t = nt_;
     if (t >= end) break;
   }
-  flush_amax(p.y_amax, am, reinterpret_cast<float*>(tile));
+  publish_amax<4>(p.y_amax, am, reinterpret_cast<float*>(tile));
 }
 
 // ----------------------------------------------------------------------------
@@ -862,7 +862,7 @@ int run_conv(ConvParams p, hipStream_t s, int nsplit = 1) {
   p.ntiles = (int)nt;
   const size_t lds = (size_t)G::IZ * G::IY(TY) * (CK / 4) * G::IX * 16;
   p.ntp = NT * nsplit;
-  return launch_tiles(conv3d_mfma_kernel<S, NT, TM, CK, KZ, KXY, DIL>, p, lds, s, 512 / nsplit, nsplit);
+  return launch_tiles<conv3d_mfma_kernel<S, NT, TM, CK, KZ, KXY, DIL>>(p, lds, s, 512 / nsplit, nsplit);
 }
 
 // Section 2 of a packed weight buffer (the pre-split bf16 planes), present for the shapes the
@@ -934,7 +934,7 @@ int run_deconv(ConvParams p, hipStream_t s) {
   if (nt >= (1L << 30)) return DSM_ERR_UNSUPPORTED;
   p.ntiles = (int)nt;
   const size_t lds = (size_t)2 * (TY + 1) * (CK / 4) * 33 * 16;
-  return launch_tiles(deconv3d_mfma_kernel<NT, CK>, p, lds, s, 512);
+  return launch_tiles<deconv3d_mfma_kernel<NT, CK>>(p, lds, s, 512);
 }
 
 }  // namespace

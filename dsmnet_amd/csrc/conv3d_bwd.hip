@@ -19,16 +19,10 @@
 // output tiles; wave w owns taps {w, w+4, ...} (<= 7 accumulators); partial sums leave as
 // fp32 atomics into a [pair][tap][c][g] workspace (g contiguous: 128-B segments), which a last
 // small kernel permutes into torch's (G, C, 3, 3, 3).
-#include "common.hpp"
-#include <type_traits>
+#include "split_core.hpp"    // static_for, Prec / split_pair / mma32, split_scale: shared with the forward kernels
 
 namespace {
 constexpr int NT_ = 256;
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void sfor(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); sfor<I + 1, N>(f); }
-}
 
 struct WgradParams {
   const float* x; const float* g; float* ws;      // ws: [npair][27][32][32]
@@ -102,7 +96,7 @@ __global__ __launch_bounds__(NT_, 1) void conv3d_wgrad_kernel(WgradParams p) {
     }
     __syncthreads();
     // wave w: taps w, w+4, ...; per tap K = TY*32 voxels, two per MFMA (k = h)
-    sfor<0, NACC>([&](auto ac) {
+    static_for<0, NACC>([&](auto ac) {
       constexpr int a = decltype(ac)::value;
       const int tap = KZ == 3 ? wave + 4 * a : a;
       if (tap < NTAP) {
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(NT_, 1) void conv3d_wgrad_kernel(WgradParams p) {
     });
   }
   // flush: ws[pair][tap][c][g] += acc  (row = c, column = g on the lanes)
-  sfor<0, NACC>([&](auto ac) {
+  static_for<0, NACC>([&](auto ac) {
     constexpr int a = decltype(ac)::value;
     const int tap = KZ == 3 ? wave + 4 * a : a;
     if (tap < NTAP) {
@@ -143,88 +137,12 @@ __global__ __launch_bounds__(NT_, 1) void conv3d_wgrad_kernel(WgradParams p) {
 // one ds_write_b64 per plane per staged f32x4) and ds_read_b64_tr_b16 hands lane (channel) four
 // voxels per read -- and since every lane supplies its own row address, the tap shift (any dx, any
 // stride) is just another row offset: no shifted copies, no alignment cases.
-typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
 typedef short ws16x4 __attribute__((ext_vector_type(4)));
 typedef short ws16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned wu32x2 __attribute__((ext_vector_type(2)));
 
-typedef _Float16 wf16x8 __attribute__((ext_vector_type(8)));
-
-// precision modes as in conv_split.hpp: PM = 3 bf16x3 (six MFMAs per product), PM = 2 f16x2 (the
-// power-of-two-scaled operand as two fp16 terms, three MFMAs), PM = 1 f16 (one MFMA)
-template <int PM> struct WPrec;
-template <> struct WPrec<3> { static constexpr int NP = 3; typedef wbf16x8 frag; };
-template <> struct WPrec<2> { static constexpr int NP = 2; typedef wf16x8 frag; };
-template <> struct WPrec<1> { static constexpr int NP = 1; typedef wf16x8 frag; };
-
-__device__ __forceinline__ int w_amax_exponent(float amax) {      // conv_common.hpp: dsm_amax_exponent
-  const int ex = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu) - 127;
-  const int e = 12 - ex;
-  return e < -60 ? -60 : (e > 60 ? 60 : e);
-}
-__device__ __forceinline__ float w_pow2f(int e) { return __builtin_bit_cast(float, (unsigned)(e + 127) << 23); }
-
-// four fp32 values -> their NP planes (two dwords per plane); `sx`: the tensor's power-of-two scale (PM < 3)
-template <int PM>
-__device__ __forceinline__ void wsplit4(const f32x4 v, float sx, wu32x2 (&pl)[WPrec<PM>::NP]) {
-  if constexpr (PM == 3) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    float r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      unsigned u[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const f2 t = {r[2 * i], r[2 * i + 1]};
-        u[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, b2));
-        if (k < 2) {
-          r[2 * i] -= __builtin_bit_cast(float, u[i] << 16);
-          r[2 * i + 1] -= __builtin_bit_cast(float, u[i] & 0xffff0000u);
-        }
-      }
-      pl[k] = wu32x2{u[0], u[1]};
-    }
-  } else {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const float r[4] = {v.x, v.y, v.z, v.w};
-    unsigned hi[2], lo[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi[i]) : "v"(r[2 * i]), "s"(sx));
-      asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi[i]) : "v"(r[2 * i + 1]), "s"(sx));
-      if constexpr (PM == 2) {
-        float r0, r1;
-        asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r0) : "v"(r[2 * i]), "s"(sx), "v"(hi[i]));
-        asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1) : "v"(r[2 * i + 1]), "s"(sx), "v"(hi[i]));
-        const f2 t = {r0, r1};
-        lo[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, h2));
-      }
-    }
-    pl[0] = wu32x2{hi[0], hi[1]};
-    if constexpr (PM == 2) pl[1] = wu32x2{lo[0], lo[1]};
-  }
-}
-
-template <int PM>
-__device__ __forceinline__ void wmma(f32x16& c, const typename WPrec<PM>::frag (&x)[WPrec<PM>::NP],
-                                     const typename WPrec<PM>::frag (&g)[WPrec<PM>::NP]) {
-  if constexpr (PM == 3) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], g[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[2], g[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], g[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], g[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], g[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], g[0], c, 0, 0, 0);
-  } else if constexpr (PM == 2) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[1], g[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[0], g[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[0], g[0], c, 0, 0, 0);
-  } else {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[0], g[0], c, 0, 0, 0);
-  }
-}
+// Precision modes, operand split, MFMA term order and power-of-two scaling are the forward kernels' own
+// (split_core.hpp: Prec, split_pair, mma32, split_scale): what the gradient rounds and how it scales cannot
+// drift from the forward.  PM = 3 bf16x3 (six MFMAs per product), PM = 2 f16x2 (three), PM = 1 f16 (one).
 
 // eight voxels (rows row0 .. row0 + 7*RS, RS rows apart) of this lane's channel: two transposed reads
 template <int RS, typename FR>
@@ -248,21 +166,19 @@ struct WgradGeo {
 
 template <int PM, int S, int TY, int KZ, int DIL>
 __global__ __launch_bounds__(NT_, 1) void wgrad_split_kernel(WgradParams p) {
-  constexpr int NP = WPrec<PM>::NP;
-  using frag = typename WPrec<PM>::frag;
+  constexpr int NP = Prec<PM>::NP;
+  using frag = typename Prec<PM>::frag;
   using G = WgradGeo<S, TY, KZ, DIL, NP>;
   constexpr int IY = G::IY, IX = G::IX, NGV = G::NGV, XPL = G::XPL, GPL = G::GPL;
   constexpr int NTAP = G::NTAP, NACC = G::NACC;
   extern __shared__ __attribute__((aligned(16))) unsigned char wl[];
   unsigned char* const xt = wl;                    // [plane][voxel (z, y, x)][32 ch] 16-bit
   unsigned char* const gt = wl + NP * XPL;         // [plane][voxel (y, x)][32 ch] 16-bit
-  float sxs = 1.f, sgs = 1.f, so = 1.f;            // operand scales and the output factor (PM < 3)
-  if constexpr (PM != 3) {
-    const int ex = w_amax_exponent(*p.x_amax), eg = w_amax_exponent(*p.g_amax);
-    sxs = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w_pow2f(ex))));
-    sgs = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w_pow2f(eg))));
-    so = w_pow2f(-(ex + eg));
-  }
+  // operand scales and the output factor (PM < 3): here BOTH operands are activations and are split in the kernel
+  const SplitScale ss = split_scale<PM>(p.x_amax, p.g_amax);
+  const float sxs = ss.sx, so = ss.out;
+  float sgs = 1.f;                                 // the second operand's own scale 2^eg: split_scale folds eg into
+  if constexpr (PM != 3) sgs = dsm_pow2f_uniform(dsm_amax_exponent(*p.g_amax));   // `out` only (a forward's weights are pre-scaled)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int pair = blockIdx.y;
@@ -316,11 +232,12 @@ __global__ __launch_bounds__(NT_, 1) void wgrad_split_kernel(WgradParams p) {
     for (int i = 0; i < NXR; ++i) {
       const int e = tid + i * NT_;
       if (e < PE) {
-        wu32x2 pl[NP];
-        wsplit4<PM>(src[i], sxs, pl);
+        unsigned lo[NP], hi[NP];
+        split_pair<PM>(src[i].x, src[i].y, sxs, lo);
+        split_pair<PM>(src[i].z, src[i].w, sxs, hi);
 #pragma unroll
         for (int k = 0; k < NP; ++k)
-          *reinterpret_cast<wu32x2*>(xt + k * XPL + (slot * (IY * IX) + (e >> 3)) * 64 + (e & 7) * 8) = pl[k];
+          *reinterpret_cast<u32x2*>(xt + k * XPL + (slot * (IY * IX) + (e >> 3)) * 64 + (e & 7) * 8) = u32x2{lo[k], hi[k]};
       }
     }
   };
@@ -342,10 +259,11 @@ __global__ __launch_bounds__(NT_, 1) void wgrad_split_kernel(WgradParams p) {
     for (int i = 0; i < NGR; ++i) {
       const int e = tid + i * NT_;
       if (e < NGV * 8) {
-        wu32x2 pl[NP];
-        wsplit4<PM>(src[i], sgs, pl);
+        unsigned lo[NP], hi[NP];
+        split_pair<PM>(src[i].x, src[i].y, sgs, lo);
+        split_pair<PM>(src[i].z, src[i].w, sgs, hi);
 #pragma unroll
-        for (int k = 0; k < NP; ++k) *reinterpret_cast<wu32x2*>(gt + k * GPL + (e >> 3) * 64 + (e & 7) * 8) = pl[k];
+        for (int k = 0; k < NP; ++k) *reinterpret_cast<u32x2*>(gt + k * GPL + (e >> 3) * 64 + (e & 7) * 8) = u32x2{lo[k], hi[k]};
       }
     }
   };
@@ -410,12 +328,12 @@ __global__ __launch_bounds__(NT_, 1) void wgrad_split_kernel(WgradParams p) {
     read_x(xf[0], xoff_of(kb0) + xtap[0]);
     static_assert(NKB % 2 == 0 && (KZ == 3 || (NKB / 4) % 2 == 0), "k-blocks are walked in pairs");
     for (int kb2 = kb0; kb2 < kb1; kb2 += 2) {
-      sfor<0, 2>([&](auto kc) {
+      static_for<0, 2>([&](auto kc) {
         constexpr int par = decltype(kc)::value;    // G fragment buffer of this k-block
         const int kb = kb2 + par;
         const int kbn = kb + 1 < kb1 ? kb + 1 : kb; // the last block re-reads itself (discarded)
         const int xoff = xoff_of(kb), xoffn = xoff_of(kbn);
-        sfor<0, NACC>([&](auto ac) {
+        static_for<0, NACC>([&](auto ac) {
           constexpr int a = decltype(ac)::value;
           constexpr int xp = (a + NACC * par) & 1;  // X fragment buffer of step (kb, a): NACC is odd
           static_assert(NACC % 2 == 1, "");
@@ -426,7 +344,7 @@ __global__ __launch_bounds__(NT_, 1) void wgrad_split_kernel(WgradParams p) {
             read_x(xf[xp ^ 1], xoffn + xtap[0]);
           }
           __builtin_amdgcn_sched_barrier(0);         // the next step's reads stay ahead of these MFMAs
-          wmma<PM>(acc[a], xf[xp], gf[par]);
+          mma32<PM>(acc[a], xf[xp], gf[par]);         // X as the A operand (rows = c), G as B
           __builtin_amdgcn_sched_barrier(0);
         });
       });
@@ -438,10 +356,10 @@ __global__ __launch_bounds__(NT_, 1) void wgrad_split_kernel(WgradParams p) {
     // dead now), four taps per round, so that each (tap, c, g) leaves as ONE atomic per workgroup
     float* const fold = reinterpret_cast<float*>(wl);          // [wave][4 taps][16][64]
     static_assert(4 * 4 * 16 * 64 * 4 <= G::LDS, "fold buffer");
-    sfor<0, 3>([&](auto rc) {
+    static_for<0, 3>([&](auto rc) {
       constexpr int rnd = decltype(rc)::value;
       __syncthreads();
-      sfor<0, 4>([&](auto jc) {
+      static_for<0, 4>([&](auto jc) {
         constexpr int j = decltype(jc)::value, a = 4 * rnd + j;
         if constexpr (a < NTAP) {
 #pragma unroll
@@ -465,7 +383,7 @@ __global__ __launch_bounds__(NT_, 1) void wgrad_split_kernel(WgradParams p) {
     return;
   }
   // flush: ws[pair][tap][c][g] += acc  (row = c, column = g on the lanes)
-  sfor<0, NACC>([&](auto ac) {
+  static_for<0, NACC>([&](auto ac) {
     constexpr int a = decltype(ac)::value;
     const int tap = KZ == 3 ? wave + 4 * a : a;
     if (tap < NTAP) {
@@ -505,7 +423,7 @@ inline void wgrad_zero(float* ws, long n, hipStream_t s) {
 
 template <int PM, int S, int TY, int KZ, int DIL>
 int launch_wgrad_split(WgradParams p, float* dw, int force_bx, hipStream_t s) {
-  using G = WgradGeo<S, TY, KZ, DIL, WPrec<PM>::NP>;
+  using G = WgradGeo<S, TY, KZ, DIL, Prec<PM>::NP>;
   static_assert(G::LDS <= 160 * 1024, "LDS");
   static_assert(KZ == 3 || (TY * 2) % 4 == 0, "KZ = 1 splits the k-blocks over the four waves");
   wgrad_zero(p.ws, (long)p.npair * G::NTAP * 32 * 32, s);
@@ -516,13 +434,7 @@ int launch_wgrad_split(WgradParams p, float* dw, int force_bx, hipStream_t s) {
   int bx = 256 / p.npair; if (bx < 1) bx = 1;
   if (force_bx > 0) bx = force_bx;                 // flags bits 16..31: the persistent grid size, forced
   if (bx > p.ntiles) bx = p.ntiles;
-  static thread_local bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute((const void*)wgrad_split_kernel<PM, S, TY, KZ, DIL>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS) != hipSuccess)
-      return DSM_ERR_LAUNCH;
-    configured = true;
-  }
+  DSM_REQUIRE((dsm_allow_lds<wgrad_split_kernel<PM, S, TY, KZ, DIL>>(G::LDS) == DSM_OK), DSM_ERR_LAUNCH);
   hipLaunchKernelGGL((wgrad_split_kernel<PM, S, TY, KZ, DIL>), dim3(bx, p.npair), dim3(NT_), G::LDS, s, p);
   const long n = (long)p.Cx * p.Cg * G::NTAP;
   hipLaunchKernelGGL(wgrad_permute_kernel, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s,
@@ -544,13 +456,7 @@ int launch_wgrad(WgradParams p, float* dw, int force_bx, hipStream_t s) {
   int bx = 256 / p.npair; if (bx < 1) bx = 1;
   if (force_bx > 0) bx = force_bx;                 // flags bits 16..31: the persistent grid size, forced
   if (bx > p.ntiles) bx = p.ntiles;
-  static thread_local bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute((const void*)conv3d_wgrad_kernel<S, TY, KZ, DIL>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return DSM_ERR_LAUNCH;
-    configured = true;
-  }
+  DSM_REQUIRE((dsm_allow_lds<conv3d_wgrad_kernel<S, TY, KZ, DIL>>(lds) == DSM_OK), DSM_ERR_LAUNCH);
   hipLaunchKernelGGL((conv3d_wgrad_kernel<S, TY, KZ, DIL>), dim3(bx, p.npair), dim3(NT_), lds, s, p);
   const long n = (long)p.Cx * p.Cg * NTAP;
   hipLaunchKernelGGL(wgrad_permute_kernel, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s,

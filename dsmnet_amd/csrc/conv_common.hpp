@@ -1,8 +1,7 @@
 // Shared pieces of the convolution translation units (conv3d.hip: fp32-input MFMA + bf16x3
 // kernels; conv_f16.hip: the fp16 split kernels): tile walk, epilogue, buffer loads, launch helper.
 #pragma once
-#include "common.hpp"
-#include <type_traits>
+#include "split_core.hpp"    // static_for, Prec / split_pair / mma32, the exponent rule, track_amax / publish_amax
 
 namespace dsmk {
 
@@ -180,17 +179,6 @@ using dsmk::ZsParams;
 using dsmk::BbParams;
 using dsmk::WideParams;
 
-// Compile-time loop: f(integral_constant<int, I>) for I in [I0, N).  Used where an index must
-// be a constant expression so that accumulator arrays stay in registers (a runtime-indexed
-// ext-vector array goes to scratch).
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 constexpr int NTHREADS = 256;
 
 // Input-tile geometry for an output tile of TY rows x 32 columns, one z.
@@ -209,55 +197,6 @@ template <int S, int KZ = 3, int KXY = 3, int DIL = 1> struct Geo {
     return S == 1 ? x : ((x & 1) * XE + (x >> 1));
   }
 };
-
-
-
-// Power-of-two scaling of the fp16 split kernels: e such that amax * 2^e lies in [2^12, 2^13)
-// (fp16 overflows at 2^16), clamped so that 2^-(ex + ew) stays a normal float.
-__host__ __device__ __forceinline__ int dsm_amax_exponent(float amax) {
-  const int ex = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu) - 127;
-  const int e = 12 - ex;
-  return e < -60 ? -60 : (e > 60 ? 60 : e);
-}
-__host__ __device__ __forceinline__ float dsm_pow2f(int e) {
-  return __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
-}
-
-// max |y| of a launch: a running maximum per thread in the epilogue; at the end one wave reduction,
-// one LDS exchange between the workgroup's four waves and ONE atomic per workgroup (non-negative
-// floats order like their bit patterns) -- and none at all when the slot already holds as much
-// (hundreds of same-address atomics per launch serialise in L2).  `lds4`: four floats of LDS no
-// wave still reads (the call is preceded by a barrier of its own).
-__device__ __forceinline__ void flush_amax(float* slot, float am, float* lds4) {
-  if (!slot) return;                                   // uniform
-#pragma unroll
-  for (int o = 32; o; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = am;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    am = fmaxf(fmaxf(lds4[0], lds4[1]), fmaxf(lds4[2], lds4[3]));
-    if (am > __builtin_nontemporal_load(slot))
-      atomicMax(reinterpret_cast<unsigned*>(slot), __builtin_bit_cast(unsigned, am));
-  }
-}
-// the same for a workgroup of eight waves (the kernels with MFMA waves and staging waves)
-__device__ __forceinline__ void flush_amax8(float* slot, float am, float* lds8) {
-  if (!slot) return;                                   // uniform
-#pragma unroll
-  for (int o = 32; o; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds8[threadIdx.x >> 6] = am;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    am = fmaxf(fmaxf(fmaxf(lds8[0], lds8[1]), fmaxf(lds8[2], lds8[3])), fmaxf(fmaxf(lds8[4], lds8[5]), fmaxf(lds8[6], lds8[7])));
-    if (am > __builtin_nontemporal_load(slot))
-      atomicMax(reinterpret_cast<unsigned*>(slot), __builtin_bit_cast(unsigned, am));
-  }
-}
-__device__ __forceinline__ void track_amax(float& am, const f32x4 v) {
-  am = fmaxf(fmaxf(am, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-}
 
 // XCD-aware persistent tile order: workgroups are dealt round-robin over the 8
 // XCDs, so worker (xcd = id % 8, slot = id / 8) walks a contiguous eighth of the
@@ -366,20 +305,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
 
 
 
-template <typename K>
-int launch_tiles(K kernel, const ConvParams& p, size_t lds, hipStream_t s, int max_blocks, int ny = 1) {
-  if (lds > 64 * 1024) {
-    static thread_local const void* configured[48];
-    static thread_local int nconf = 0;
-    bool seen = false;
-    for (int i = 0; i < nconf; ++i) seen |= (configured[i] == (const void*)kernel);
-    if (!seen) {
-      if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds) != hipSuccess)
-        return DSM_ERR_LAUNCH;
-      if (nconf < 48) configured[nconf++] = (const void*)kernel;
-    }
-  }
+template <auto kernel>
+int launch_tiles(const ConvParams& p, size_t lds, hipStream_t s, int max_blocks, int ny = 1) {
+  if (lds > 64 * 1024 && dsm_allow_lds<kernel>(lds) != DSM_OK) return DSM_ERR_LAUNCH;
   if (p.force_blocks) max_blocks = p.force_blocks;     // dsm_conv3d_args.flags: persistent-grid A/B runs
   int blocks = p.ntiles < max_blocks ? p.ntiles : max_blocks;
   if (blocks >= 8) blocks &= ~7;                 // whole rounds over the 8 XCDs

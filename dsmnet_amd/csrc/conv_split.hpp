@@ -1,19 +1,8 @@
 // Split-operand kernels: fp32 convolution and transposed convolution on the 16-bit matrix pipe.
 // Included by conv3d.hip (PM = 3) and conv_f16.hip (PM = 2, 1) after conv_common.hpp.
 //
-// PM (precision mode) = number of 16-bit terms an fp32 operand is split into:
-//   PM = 3  "bf16x3": v = hi + mid + lo in bf16 (exact split), six MFMAs per product -- fp32 accuracy,
-//           no scaling needed (bf16 has the fp32 exponent range);
-//   PM = 2  "f16x2":  v * 2^e = hi + lo in fp16 (22 significand bits), three MFMAs per product
-//           (wl xh + wh xl + wh xh) -- fp32 accuracy at half the MFMAs.  fp16 has a 5-bit exponent,
-//           so every tensor is scaled by a power of two chosen from its absolute maximum (activations:
-//           a device scalar written by the producing kernel's epilogue, dsm_conv3d_args.x_amax /
-//           y_amax; weights: at pack time) so that the maximum lands in [2^12, 2^13); the combined
-//           2^-(ex + ew) is folded into the epilogue's scale.  Residuals that fall below fp16's normal
-//           range become subnormals (absolute error 2^-25 against a maximum of 2^12), which the MFMA
-//           keeps (f16 denormals are not flushed on gfx950: tests/test_f16_gpu.py);
-//   PM = 1  "f16":    operands rounded to fp16 (hi only), one MFMA per product, fp32 accumulate --
-//           the reduced-precision mode of BASELINE config #5.
+// PM (precision mode) = number of 16-bit terms an fp32 operand is split into: 3 bf16x3, 2 f16x2, 1 f16.  The modes,
+// the split, the MFMA term order and the power-of-two scaling are defined in split_core.hpp.
 #pragma once
 
 #ifndef DSM_STAMP
@@ -21,85 +10,9 @@
 #define DSM_STAMP_INIT() do {} while (0)
 #endif
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-template <int PM> struct Prec;
-template <> struct Prec<3> { static constexpr int NP = 3, NPW = 3; typedef bf16x8 frag; };
-template <> struct Prec<2> { static constexpr int NP = 2, NPW = 2; typedef f16x8 frag; };
-template <> struct Prec<1> { static constexpr int NP = 1, NPW = 2; typedef f16x8 frag; };   // reads plane 0 of the f16x2 packing
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {        // low half = a
-  const f32x2 t = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
-// two fp32 values -> their NP planes (one dword per plane, low half = a).  PM < 3: `sx` = 2^ex.
+// scaling of a launch from the maxima its arguments name (split_core.hpp)
 template <int PM>
-__device__ __forceinline__ void split_pair(float a, float b, float sx, unsigned (&pl)[Prec<PM>::NP]) {
-  if constexpr (PM == 3) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      pl[q] = pack_bf16(a, b);
-      if (q < 2) { a -= bf16_lo(pl[q]); b -= bf16_hi(pl[q]); }
-    }
-  } else {
-    // hi = f16(v * sx) straight from the fp32 value (v_fma_mix{lo,hi}_f16: an fp32 fma -- exact, sx is a
-    // power of two -- rounded once to fp16), the residual with hi read as an fp16 operand
-    // (v_fma_mix_f32): five plain VALU instructions per pair and no packed-fp32 ones, which issue
-    // slowly beside an MFMA stream (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
-    unsigned hi;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(a), "s"(sx));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(b), "s"(sx));
-    pl[0] = hi;
-    if constexpr (PM == 2) {
-      float r0, r1;
-      asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r0) : "v"(a), "s"(sx), "v"(hi));
-      asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1) : "v"(b), "s"(sx), "v"(hi));
-      const f32x2 r = {r0, r1};
-      pl[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-    }
-  }
-}
-
-// one 32x32x16 product group: c += w * x on PM terms (small terms first)
-template <int PM>
-__device__ __forceinline__ void mma32(f32x16& c, const typename Prec<PM>::frag (&w)[Prec<PM>::NP],
-                                      const typename Prec<PM>::frag (&x)[Prec<PM>::NP]) {
-  if constexpr (PM == 3) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[1], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[2], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], x[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], x[0], c, 0, 0, 0);
-  } else if constexpr (PM == 2) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0], x[0], c, 0, 0, 0);
-  } else {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[0], x[0], c, 0, 0, 0);
-  }
-}
-
-// scaling of a launch (PM < 3): sx = 2^ex multiplies the staged activations, `out` = 2^-(ex + ew)
-// is folded into the epilogue's scale
-struct SplitScale { float sx, out; };
-template <int PM>
-__device__ __forceinline__ SplitScale split_scale(const ConvParams& p) {
-  if constexpr (PM == 3) return SplitScale{1.f, 1.f};
-  else {
-    const int ex = dsm_amax_exponent(*p.x_amax), ew = dsm_amax_exponent(*p.w_amax);
-    return SplitScale{__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, dsm_pow2f(ex)))),
-                      dsm_pow2f(-(ex + ew))};
-  }
-}
+__device__ __forceinline__ SplitScale split_scale(const ConvParams& p) { return split_scale<PM>(p.x_amax, p.w_amax); }
 
 // Folded-BN scale / shift of a launch, staged once into LDS behind the two images: the epilogue
 // reads them with LDS latency instead of an L2 round trip per tile (stamps: the epilogue was 15 %
@@ -454,7 +367,7 @@ void conv_split_kernel(ConvParams p) {
     cur_pos = nxt; cur ^= 1;
     if (cur_pos.t >= end) break;
   }
-  flush_amax(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
+  publish_amax<4>(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
 }
 
 // ----------------------------------------------------------------------------
@@ -635,7 +548,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_once_kernel(ConvParams p) {
       store_tile<COUT>(acc[m][n], af, p.relu, p.y + vox * COUT + cbase, rr[m], p.res != nullptr, am);
     }
   }
-  flush_amax(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
+  publish_amax<4>(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
 }
 
 // ----------------------------------------------------------------------------
@@ -853,7 +766,7 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p) {
       if (i >= nchunks) break;
     }
   }
-  flush_amax8(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
+  publish_amax<8>(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
 }
 
 // ----------------------------------------------------------------------------
@@ -1100,7 +1013,7 @@ __global__ __launch_bounds__(NTHREADS, (DeconvSplitCfg<PM, NT>::WGS)) void decon
     cur_pos = nxt; cur ^= 1;
     if (cur_pos.t >= end) break;
   }
-  flush_amax(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
+  publish_amax<4>(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
 }
 
 // weights -> the split section of a packed buffer: [Cin/16][tap][Cout/32][plane NPW][lane][8 x 16-bit],
@@ -1140,7 +1053,7 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
     track_amax(am, reinterpret_cast<const f32x4*>(x)[i]);
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) am = fmaxf(am, fabsf(x[(n4 << 2) + threadIdx.x]));
   __shared__ float red[4];
-  flush_amax(out, am, red);
+  publish_amax<4>(out, am, red);
 }
 
 // ---------------------------------------------------------------------------- launch helpers
@@ -1152,8 +1065,7 @@ int run_conv_split(ConvParams p, hipStream_t s) {
   if (nt >= (1L << 30)) return DSM_ERR_UNSUPPORTED;
   p.ntiles = (int)nt;
   // two images; one workgroup per CU, or two where conv_split_two_per_cu says both fit
-  return launch_tiles(conv_split_kernel<PM, NT, TM, KZ, DIL, S, NSPLIT>, p, C::LDS, s,
-                      (C::TWO ? 512 : 256) / NSPLIT, NSPLIT);
+  return launch_tiles<conv_split_kernel<PM, NT, TM, KZ, DIL, S, NSPLIT>>(p, C::LDS, s, (C::TWO ? 512 : 256) / NSPLIT, NSPLIT);
 }
 
 template <int PM, int NT, int TM, int NCH, int NSPLIT>
@@ -1175,12 +1087,7 @@ int run_conv_s2(ConvParams p, hipStream_t s) {
   const long nt = (long)p.B * p.Do * p.nty * p.ntx;
   if (nt >= (1L << 30)) return DSM_ERR_UNSUPPORTED;
   p.ntiles = (int)nt;
-  static thread_local bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute((const void*)conv_s2_kernel<PM>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-      return DSM_ERR_LAUNCH;
-    configured = true;
-  }
+  DSM_REQUIRE(dsm_allow_lds<conv_s2_kernel<PM>>(C::LDS) == DSM_OK, DSM_ERR_LAUNCH);
   int blocks = p.force_blocks ? p.force_blocks : 256;          // one workgroup per CU
   if (blocks > p.ntiles) blocks = p.ntiles;
   if (blocks >= 8) blocks &= ~7;                               // whole rounds over the 8 XCDs
@@ -1195,7 +1102,7 @@ int run_deconv_split(ConvParams p, hipStream_t s) {
   const long nt = (long)p.B * p.Di * p.nty * p.ntx * 2;       // x2: z-parity
   if (nt >= (1L << 30)) return DSM_ERR_UNSUPPORTED;
   p.ntiles = (int)nt;
-  return launch_tiles(deconv_split_kernel<PM, NT>, p, C::LDS, s, 256 * C::WGS);
+  return launch_tiles<deconv_split_kernel<PM, NT>>(p, C::LDS, s, 256 * C::WGS);
 }
 
 // plan kinds 5 (convolution) and 6 (transposed convolution) at precision mode PM

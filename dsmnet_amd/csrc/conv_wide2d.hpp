@@ -64,9 +64,8 @@ __global__ __launch_bounds__(512, 2) void conv_wide2d_kernel(WideParams p) {
   const int NCH = p.Cin >> 4, NT = p.Cout >> 5;
   const int M = p.B * p.Ho * p.Wo;
 
-  const int ex = dsm_amax_exponent(*p.x_amax), ew = dsm_amax_exponent(*p.w_amax);
-  const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, dsm_pow2f(ex))));
-  const float so = dsm_pow2f(-(ex + ew));
+  const SplitScale ss = split_scale<PM>(p.x_amax, p.w_amax);
+  const float sx = ss.sx, so = ss.out;
   const __amdgpu_buffer_rsrc_t xrs = make_rsrc(p.x, p.xbytes), wrs = make_rsrc(p.w, p.wbytes);
   const unsigned WTAP = (unsigned)NT * NPW * 1024u;    // weight bytes per (chunk, tap)
   const unsigned WCH = 9u * WTAP;
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void conv_wide2d_kernel(WideParams p) {
           store_tile<0>(acc[i], af, p.relu, p.y + (long)opix[i] * p.Cout + cbase, (const float*)nullptr, am);
     }
   }
-  if (p.ksplit == 1) flush_amax8(p.y_amax, am, red);
+  if (p.ksplit == 1) publish_amax<8>(p.y_amax, am, red);
 }
 
 // The K-ranges' partial sums, added in index order; scale / shift / ReLU; y and max |y|.
@@ -218,7 +217,7 @@ __global__ __launch_bounds__(256) void wide2d_reduce_kernel(WideParams p) {
   __shared__ float red[4];
   const long nq = (long)p.B * p.Ho * p.Wo * (p.Cout >> 2);
   const int cq = p.Cout >> 2;
-  const float so = dsm_pow2f(-(dsm_amax_exponent(*p.x_amax) + dsm_amax_exponent(*p.w_amax)));
+  const float so = split_scale<2>(p.x_amax, p.w_amax).out;           // the fp16 modes share it
   const f32x4* const ws = reinterpret_cast<const f32x4*>(p.ws);
   float am = 0.f;
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
@@ -233,18 +232,13 @@ __global__ __launch_bounds__(256) void wide2d_reduce_kernel(WideParams p) {
     reinterpret_cast<f32x4*>(p.y)[q] = v;
     track_amax(am, v);
   }
-  flush_amax(p.y_amax, am, red);
+  publish_amax<4>(p.y_amax, am, red);
 }
 
 template <int PM, bool TR = false>
 int launch_conv_wide2d(const WideParams& p, int grid, hipStream_t s) {
   using Cf = WideCfg<PM>;
-  static thread_local bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute((const void*)conv_wide2d_kernel<PM, TR>, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS) != hipSuccess)
-      return DSM_ERR_LAUNCH;
-    configured = true;
-  }
+  DSM_REQUIRE((dsm_allow_lds<conv_wide2d_kernel<PM, TR>>(Cf::LDS) == DSM_OK), DSM_ERR_LAUNCH);
   hipLaunchKernelGGL((conv_wide2d_kernel<PM, TR>), dim3((unsigned)grid), dim3(Cf::THREADS), Cf::LDS, s, p);
   if (p.ksplit > 1) {
     const long nq = (long)p.B * p.Ho * p.Wo * (p.Cout >> 2);

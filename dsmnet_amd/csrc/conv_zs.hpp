@@ -1,5 +1,5 @@
 // The z-sliding convolution: Conv3d(k3, s1, p1), Cin % 32 == 0 -> Cout = 32, fp32 tensors, on the
-// 16-bit matrix pipe at precision mode PM (conv_split.hpp: 3 = bf16x3, 2 = f16x2, 1 = f16).
+// 16-bit matrix pipe at precision mode PM (split_core.hpp: 3 = bf16x3, 2 = f16x2, 1 = f16).
 // Included by conv3d.hip (PM = 3) and conv_f16.hip (PM = 2, 1) after conv_split.hpp.
 //
 // Replaces convbn_3d + ReLU + myadd_3d of models/psmnet/submodule.py:16-19 and
@@ -35,7 +35,7 @@
 //    One barrier per chunk; images and exchange buffers are double-buffered.
 //  * staging: a chunk = one input plane x 32 channels, (TY + 2) x 34 voxels x 8 fp32 quads = NPF
 //    buffer loads per staging thread (zero address VALU: per-column offsets, per-chunk descriptor
-//    base).  Each quad is split into its NP 16-bit planes (conv_split.hpp split_pair: the operand
+//    base).  Each quad is split into its NP 16-bit planes (split_core.hpp split_pair: the operand
 //    split of this precision mode) and written to the LDS image [plane][g = quad & 3][voxel][16 B]
 //    -- the operand order of v_mfma_f32_16x16x32: lane (g, x) of the B operand reads the 16-byte
 //    unit (g, voxel x), element e of which is channel 16 (e >> 2) + 4 g + (e & 3) of the group.
@@ -115,14 +115,10 @@ __global__ __launch_bounds__(512, 1) void conv_zs_kernel(ZsParams p) {
   const long u_begin = p.nunits * logical / G, u_end = p.nunits * (logical + 1) / G;
   if (u_begin >= u_end) return;
 
-  // power-of-two scaling of the fp16 modes (conv_split.hpp) and the folded-BN affine of this
+  // power-of-two scaling of the fp16 modes (split_core.hpp) and the folded-BN affine of this
   // lane's 4 channels (16 ah + 4 g + i), the output factor folded into the scale
-  float sx = 1.f, so = 1.f;
-  if constexpr (PM != 3) {
-    const int ex = dsm_amax_exponent(*p.x_amax), ew = dsm_amax_exponent(*p.w_amax);
-    sx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, dsm_pow2f(ex))));
-    so = dsm_pow2f(-(ex + ew));
-  }
+  const SplitScale ss = split_scale<PM>(p.x_amax, p.w_amax);
+  const float sx = ss.sx, so = ss.out;
   unsigned char* const xch = lds_raw + 2 * IMG;
   float* const aff = reinterpret_cast<float*>(lds_raw + 2 * IMG + 2 * XCH);
   if (tid < 64) aff[tid] = tid < 32 ? (p.scale ? p.scale[tid] * so : so) : (p.shift ? p.shift[tid - 32] : 0.f);
@@ -440,19 +436,7 @@ __global__ __launch_bounds__(512, 1) void conv_zs_kernel(ZsParams p) {
     }
   }
   // ---- the tensor maximum: one atomic per workgroup
-  if (p.y_amax) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
-    float* const red = reinterpret_cast<float*>(lds_raw);
-    __syncthreads();
-    if (lane == 0) red[wave] = am;
-    __syncthreads();
-    if (tid == 0) {
-      am = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));
-      if (am > __builtin_nontemporal_load(p.y_amax))
-        atomicMax(reinterpret_cast<unsigned*>(p.y_amax), __builtin_bit_cast(unsigned, am));
-    }
-  }
+  publish_amax<8>(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
 }
 
 // weights: torch (Cout = 32, Cin, 3,3,3) -> [cg][tp = ky*3+kx][kz][a = cout/16][plane NPW][lane][8 x 16-bit]
@@ -489,13 +473,7 @@ int launch_conv_zs(ZsParams p, int grid, hipStream_t s) {
   DSM_REQUIRE(ncol < (1L << 30), DSM_ERR_UNSUPPORTED);
   p.ncol = (int)ncol;
   p.nunits = ncol * p.Do;
-  static thread_local bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute((const void*)conv_zs_kernel<PM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            C::LDS) != hipSuccess)
-      return DSM_ERR_LAUNCH;
-    configured = true;
-  }
+  DSM_REQUIRE(dsm_allow_lds<conv_zs_kernel<PM>>(C::LDS) == DSM_OK, DSM_ERR_LAUNCH);
   int blocks = grid > 0 ? grid : 256;                          // persistent workgroups: one per CU
   if ((long)blocks > p.nunits) blocks = (int)p.nunits;
   hipLaunchKernelGGL(conv_zs_kernel<PM>, dim3(blocks), dim3(C::THREADS), C::LDS, s, p);

@@ -709,13 +709,7 @@ static int corr_fwd_launch(const CorrPlan& plan, const void* fL, const void* fR,
     dim3 grid(dsm_cdiv(W, TX), H, B);
 #define DSM_CORR_TILE(S_, NDH__)                                                                     \
     do {                                                                                             \
-      static thread_local bool configured = false;                                                  \
-      if (!configured) {                                                                             \
-        if (hipFuncSetAttribute((const void*)corr1d_tile_kernel<S_, 12, NDH__, SIM>,                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) \
-          return DSM_ERR_LAUNCH;                                                                     \
-        configured = true;                                                                           \
-      }                                                                                              \
+      DSM_REQUIRE((dsm_allow_lds<corr1d_tile_kernel<S_, 12, NDH__, SIM>>(150 * 1024) == DSM_OK), DSM_ERR_LAUNCH); \
       hipLaunchKernelGGL((corr1d_tile_kernel<S_, 12, NDH__, SIM>), grid, dim3(256 * NDH__), tile_lds + 4096, s, /* + a row of slack */ \
                          (const float*)fL, (const float*)fR, raw, (const float*)inv, C, H, W, D);     \
     } while (0)
@@ -917,13 +911,7 @@ extern "C" int dsm_corr1d_sim_bwd(const void* grad_out, const void* fL, const vo
     dim3 grid(dsm_cdiv(W, TX), H, B);
 #define DSM_CORR_BWD_TILE(S_, NORM_)                                                                 \
     do {                                                                                             \
-      static thread_local bool configured = false;                                                  \
-      if (!configured) {                                                                             \
-        if (hipFuncSetAttribute((const void*)corr1d_bwd_tile_kernel<S_, NORM_>,                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) \
-          return DSM_ERR_LAUNCH;                                                                     \
-        configured = true;                                                                           \
-      }                                                                                              \
+      DSM_REQUIRE((dsm_allow_lds<corr1d_bwd_tile_kernel<S_, NORM_>>(150 * 1024) == DSM_OK), DSM_ERR_LAUNCH); \
       hipLaunchKernelGGL((corr1d_bwd_tile_kernel<S_, NORM_>), grid, dim3(256), p.lds, s, p.g,       \
                          (const float*)fL, (const float*)fR, (float*)dfL, (float*)dfR,               \
                          (const float*)p.coef, C, H, W, D);                                          \

@@ -299,9 +299,8 @@ extern "C" int dsm_concat_volume_fwd(const void* fL, const void* fR, void* vol, 
   if (plan.kind == VOL_NDHWC || plan.kind == VOL_NDHWC_BIG) {
     constexpr int TX = VOL_TX;
     const size_t lds = plan.lds;
-    if (plan.kind == VOL_NDHWC_BIG &&
-        hipFuncSetAttribute((const void*)volume_ndhwc_fwd_kernel<TX>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    // raised once to the most any plan asks for (pick_volume_fwd admits up to 160 KiB), not per launch to its size
+    if (plan.kind == VOL_NDHWC_BIG && dsm_allow_lds<volume_ndhwc_fwd_kernel<TX>>(160 * 1024) != DSM_OK)
       return DSM_ERR_LAUNCH;
     dim3 grid(dsm_cdiv(W, TX), H, B);
     hipLaunchKernelGGL(volume_ndhwc_fwd_kernel<TX>, grid, dim3(256), lds, s, l, r, v, C, H, W, D,

@@ -91,12 +91,8 @@ __global__ __launch_bounds__(512, 1) void deconv_zs_kernel(ConvParams p) {
   const long u_begin = nunits * logical / G, u_end = nunits * (logical + 1) / G;
   if (u_begin >= u_end) return;
 
-  float sx = 1.f, so = 1.f;
-  {
-    const int ex = dsm_amax_exponent(*p.x_amax), ew = dsm_amax_exponent(*p.w_amax);
-    sx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, dsm_pow2f(ex))));
-    so = dsm_pow2f(-(ex + ew));
-  }
+  const SplitScale ss = split_scale<PM>(p.x_amax, p.w_amax);
+  const float sx = ss.sx, so = ss.out;
   unsigned char* const xch = lds_raw + 2 * IMG;
   float am = 0.f;
 
@@ -409,19 +405,7 @@ __global__ __launch_bounds__(512, 1) void deconv_zs_kernel(ConvParams p) {
     }
   }
   // ---- the tensor maximum: one atomic per workgroup
-  if (p.y_amax) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
-    float* const red = reinterpret_cast<float*>(lds_raw);
-    __syncthreads();
-    if (lane == 0) red[wave] = am;
-    __syncthreads();
-    if (tid == 0) {
-      am = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));
-      if (am > __builtin_nontemporal_load(p.y_amax))
-        atomicMax(reinterpret_cast<unsigned*>(p.y_amax), __builtin_bit_cast(unsigned, am));
-    }
-  }
+  publish_amax<8>(p.y_amax, am, reinterpret_cast<float*>(lds_raw));
 }
 
 template <int PM>
@@ -434,13 +418,7 @@ int run_deconv_zs(ConvParams p, hipStream_t s) {
   DSM_REQUIRE(ncol * p.Di < (1L << 30), DSM_ERR_UNSUPPORTED);
   p.ntiles = (int)ncol;
   const long nunits = ncol * ((p.Do + 1) / 2);
-  static thread_local bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute((const void*)deconv_zs_kernel<PM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            C::LDS) != hipSuccess)
-      return DSM_ERR_LAUNCH;
-    configured = true;
-  }
+  DSM_REQUIRE(dsm_allow_lds<deconv_zs_kernel<PM>>(C::LDS) == DSM_OK, DSM_ERR_LAUNCH);
   int blocks = p.force_blocks ? p.force_blocks : 256;          // persistent workgroups: one per CU
   if ((long)blocks > nunits) blocks = (int)nunits;
   hipLaunchKernelGGL(deconv_zs_kernel<PM>, dim3(blocks), dim3(C::THREADS), C::LDS, s, p);

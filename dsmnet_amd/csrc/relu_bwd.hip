@@ -56,7 +56,7 @@ __global__ __launch_bounds__(RB_THREADS) void bias_relu_bwd_kernel(const float* 
       }
     }
   }
-  flush_amax(g_amax, am, red);
+  publish_amax<4>(g_amax, am, red);
 }
 
 // db[c] = the workgroups' partial sums, added in index order

@@ -53,11 +53,6 @@ struct Work {
   float* save;                              // [item][NSAVE][B*h*w]
 };
 
-__device__ __forceinline__ float linspace_at(float start, float end, int steps, int i) {
-  const float step = (end - start) / (float)(steps - 1);
-  return i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - i - 1);
-}
-
 __device__ __forceinline__ float sgnf(float v) { return (float)((v > 0.f) - (v < 0.f)); }
 
 // grid_sample's bilinear tap set at normalised (gx, gy) of a W0 x H0 plane
@@ -176,12 +171,6 @@ __device__ __forceinline__ void filter_tile(const Work& W, float (*reg)[RW][RW +
     for (int j = 0; j < 11; ++j) s += W.g[j] * hs[k][ty + j][tx];
     out[k] = s;
   }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void selfsup_fwd_tiles(const Work W) {

@@ -14,7 +14,7 @@
 //   sepvol_sums_kernel       F_v, G_v from the K images
 //   sepvol_broadcast_kernel  the (B, D, H, W, 32) output: F + G from LDS (general form from the K
 //                            images where it does not apply), folded BN, ReLU, max |y|
-#include "common.hpp"
+#include "split_core.hpp"    // track_amax, publish_amax
 
 namespace {
 
@@ -195,21 +195,11 @@ __global__ __launch_bounds__(256) void sepvol_broadcast_kernel(SvBroadcast p) {
       else s = sv_general(p, b, d, y, x, o4);
       s = s * sc + sh;
       if (p.relu) { s.x = fmaxf(s.x, 0.f); s.y = fmaxf(s.y, 0.f); s.z = fmaxf(s.z, 0.f); s.w = fmaxf(s.w, 0.f); }
-      am = fmaxf(fmaxf(am, fmaxf(fabsf(s.x), fabsf(s.y))), fmaxf(fabsf(s.z), fabsf(s.w)));
+      track_amax(am, s);
       if (p.plain_stores) dst[i] = s; else __builtin_nontemporal_store(s, dst + i);
     }
   }
-  if (p.y_amax) {                                      // uniform: one atomic per workgroup at most
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) am = fmaxf(am, __shfl_xor(am, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = am;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      am = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-      if (am > __builtin_nontemporal_load(p.y_amax))
-        atomicMax(reinterpret_cast<unsigned*>(p.y_amax), __builtin_bit_cast(unsigned, am));
-    }
-  }
+  publish_amax<4, false>(p.y_amax, am, red);           // `red` is the publisher's own: no barrier ahead of the write
 }
 
 }  // namespace

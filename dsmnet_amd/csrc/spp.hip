@@ -12,7 +12,7 @@
 //                        2x2 / 4x4 / 8x8 P8 pixels (equal tiling windows, floor semantics of the
 //                        reference's direct pools preserved), 1x1 conv + folded BN + ReLU
 //   spp_concat_kernel    raw, skip, branch maps -> (B,H,W,320), bilinear taps on the fly   79 MB written
-#include "common.hpp"
+#include "split_core.hpp"    // quad_amax, publish_amax
 
 namespace {
 
@@ -119,9 +119,6 @@ __device__ __forceinline__ Tap tap_at(int o, int in_size, int out_size) {
 // passes over the pixel's 80 16-byte quads -- 256 contiguous bytes per pixel and pass, the pixel's
 // coordinates and bilinear taps computed once, 32-bit index arithmetic (the first form, one flat
 // 64-bit index per quad with a division by 80 and by W, H each, spent its time in integer division).
-__device__ __forceinline__ float quad_amax(const f32x4 v) {
-  return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-}
 __global__ __launch_bounds__(256) void spp_concat_kernel(const float* __restrict__ raw,
                                                          const float* __restrict__ skip,
                                                          const float* __restrict__ br,
@@ -157,18 +154,8 @@ __global__ __launch_bounds__(256) void spp_concat_kernel(const float* __restrict
       am = fmaxf(am, quad_amax(v));
     }
   }
-  if (y_amax) {                 // uniform: one atomic per workgroup, none when the slot already holds as much
-    __shared__ float red[4];
-#pragma unroll
-    for (int o = 32; o; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = am;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      am = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-      if (am > __builtin_nontemporal_load(y_amax))
-        atomicMax(reinterpret_cast<unsigned*>(y_amax), __builtin_bit_cast(unsigned, am));
-    }
-  }
+  __shared__ float red[4];      // the publisher's own: nothing else reads it, so no barrier ahead of the write
+  publish_amax<4, false>(y_amax, am, red);
 }
 
 }  // namespace

@@ -69,12 +69,6 @@ __device__ __forceinline__ float tap_weight(const Tap& t, int c) {
 
 __device__ __forceinline__ int sgni(float v) { return (v > 0.f) - (v < 0.f); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void suploss_fwd_tiles(const Work K) {
   __shared__ float C[PH * PW];             // coarse patch (levels > 0)
   __shared__ float P[PH][PW];              // fine prediction, rows ty0-1.., columns tx0-1..

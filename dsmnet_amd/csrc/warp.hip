@@ -14,11 +14,6 @@
 
 namespace {
 
-__device__ __forceinline__ float linspace_at(float start, float end, int steps, int i) {
-  const float step = (end - start) / (float)(steps - 1);
-  return i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - i - 1);
-}
-
 __global__ __launch_bounds__(256) void warp_abs_error_kernel(
     const float* __restrict__ L, const float* __restrict__ R, const float* __restrict__ disp,
     float* __restrict__ out, int C, int H, int W, int H0, int W0, float x1, float y1, float delt,
