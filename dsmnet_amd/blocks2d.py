@@ -92,6 +92,27 @@ def _wide_ok(conv, x):
     return 4 * B * cin * H * W < 2 ** 31 and B * Ho * Wo * conv.out_channels < 2 ** 31 - 1
 
 
+# 5x5 layers profiles/conv2d_k5.md measured slower than the stock layer: (Cin, Cout)
+_K5_EXCLUDED = frozenset()
+
+
+def k5_ok(conv, x):
+    """Can ``conv`` run on the 5x5 stride-2 MFMA kernel (csrc/conv_wide2d.hpp with K = 5, plan kind 10 of
+    ``dsm_conv3d_fwd``) for input ``x``?  k5, pad 2, stride 2, dilation 1, Cin % 16 == 0, 128 or 256 outputs, an
+    fp16 precision mode; the map sizes are the plan's own answer (the host-only ``dsm_conv3d_plan``: at most
+    eight column blocks of one staged box -- output widths up to 592 --, 32-bit offsets)."""
+    if not (isinstance(conv, nn.Conv2d) and x.is_cuda and x.dtype == torch.float32):
+        return False
+    if (conv.kernel_size != (5, 5) or conv.stride != (2, 2) or conv.dilation != (1, 1) or conv.padding != (2, 2) or
+            conv.groups != 1 or conv.padding_mode != "zeros" or conv.out_channels not in cv.K5_COUT):
+        return False
+    mode = cv.get_option("conv_precision")
+    B, cin, H, W = x.shape
+    if mode not in ("f16x2", "f16") or cin % 16 != 0 or cin != conv.in_channels or (cin, conv.out_channels) in _K5_EXCLUDED:
+        return False
+    return cv.conv2d_k5_plan_ok(B, cin, conv.out_channels, H, W, mode)
+
+
 def wide_train_ok(conv, act, x):
     """Does ``Sequential(conv, act)`` train on ``costvolume.wide_conv2d_relu`` for the fp32 CUDA map ``x``?
     The option ``wide_conv2d_train``, an fp16 precision mode, nn.ReLU, k3 / dilation 1 / pad 1 / stride 1 or 2

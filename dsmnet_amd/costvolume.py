@@ -534,6 +534,7 @@ _OPTIONS = {"fuse_volume": True, "fuse_blocks": True, "conv_precision": _env_pre
             "fused_supervised_loss": _env_flag("DSM_FUSED_SUP_LOSS", True),
             "wide_conv2d": _env_flag("DSM_WIDE_CONV2D", _WIDE_CONV2D_DEFAULT),
             "wide_conv2d_train": _env_flag("DSM_WIDE_CONV2D_TRAIN", False),
+            "conv2d_k5": _env_flag("DSM_CONV2D_K5", False),
             "warp_train": _env_flag("DSM_WARP_TRAIN", False),
             "decoder_train": _env_flag("DSM_DECODER_TRAIN", False),
             "corr1d_tiled_bwd": False}
@@ -563,6 +564,10 @@ def set_option(name, value):
     ``wide_conv2d_relu`` under autograd (forward, ReLU + bias backward, backward-data and weight gradient on
     this project's kernels; fp16 modes), whatever ``wide_conv2d`` says; default off (profiles/wide2d_train.md),
     starts from DSM_WIDE_CONV2D_TRAIN=0|1;
+    ``conv2d_k5`` -- the 5x5 stride-2 layers to 128 / 256 channels with Cin % 16 == 0 (DispNet's conv2 and
+    conv3a, the conv2 of DispNetC / iResNet) run on the MFMA kernel (csrc/conv_wide2d.hpp with a 5x5 window;
+    eval, fp16 modes) instead of the stock layer; default off (profiles/conv2d_k5.md), starts from
+    DSM_CONV2D_K5=0|1;
     ``warp_train`` -- iResNet's reconstruction error ``|stemL - imwrap_BCHW(stemR, -r_pr0)|`` runs as
     ``warp_abs_error`` under autograd too (fp32 GPU tensors; csrc/warp.hip forward and backward) instead of the
     stock grid_sample chain; default off (profiles/train_ops.md), starts from DSM_WARP_TRAIN=0|1;
@@ -769,6 +774,7 @@ def carry_amax(dst, *srcs):
 
 
 WIDE2D_COUT = (256, 512, 1024)
+K5_COUT = (128, 256)            # the 5x5 stride-2 layers (plan kind 10)
 
 
 def _split_kernel_layer(a):
@@ -776,6 +782,8 @@ def _split_kernel_layer(a):
     5 / 6)?  3x3(x3) taps, Cin % 16 == 0, Cout a multiple of 32 up to 64 (3-D; 128 on small volumes at
     stride 1) / 128 (2-D); stride 1, 3-D stride 2 to 64 channels, or transposed from Cin % 32 == 0."""
     kd, k = (a.kd or 3), (a.k or 3)
+    if kd == 1 and k == 5 and a.Cin % 16 == 0 and a.Cout in K5_COUT:           # the same kernel, 5x5 (plan kind 10)
+        return (a.dil or 1) == 1 and not a.transposed and a.stride == 2
     if kd == 1 and k == 3 and a.Cin % 16 == 0 and a.Cout in WIDE2D_COUT:       # conv_wide2d.hpp (plan kinds 8, 9)
         return (a.dil or 1) == 1 and (not a.transposed or a.stride == 2)
     if k != 3 or a.Cin % 16 or a.Cout % 32 or a.Cout > 128:
@@ -833,8 +841,8 @@ def _conv_launch(x, packed_weight, scale, shift, residual, y, B, cin, cout, in_s
     keep = _set_precision(a, x, y if cout > 1 else None, mode)
     lib = _lib.load()
     ws = None
-    if kd == 1 and cout in WIDE2D_COUT:
-        # the wide layers' K-split partial sums: from torch's caching allocator, per call (no
+    if kd == 1 and (cout in WIDE2D_COUT or k == 5):
+        # the wide (and 5x5) layers' K-split partial sums: from torch's caching allocator, per call (no
         # synchronisation; inside a hipGraph capture the block belongs to the graph's pool).  Asked for
         # these layers only: the query runs the planner
         nws = lib.dsm_conv3d_workspace_bytes(ctypes.byref(a))
@@ -943,11 +951,12 @@ _CL2D = torch.channels_last
 
 def pack_conv2d_weight(weight, cin_padded=None):
     """torch Conv2d weight (Cout, Cin, k, k), k in {1, 3} -> MFMA fragment order.  ``cin_padded``
-    (a multiple of 16 >= Cin) zero-fills the extra input channels."""
+    (a multiple of 16 >= Cin) zero-fills the extra input channels.  k = 5 (Cout 128 / 256, Cin % 16 == 0): the
+    fp16 section of the 5x5 stride-2 kernel alone."""
     _require_device("pack_conv2d_weight", weight)
     cout, cin, kh, kw = weight.shape
-    if kh != kw or kh not in (1, 3):
-        raise ValueError("conv2d_block supports 1x1 and 3x3 kernels, got %dx%d" % (kh, kw))
+    if kh != kw or kh not in (1, 3, 5):
+        raise ValueError("conv2d_block supports 1x1, 3x3 and 5x5 kernels, got %dx%d" % (kh, kw))
     cin_p = cin if cin_padded is None else int(cin_padded)
     w = weight.detach().contiguous()
     lib = _lib.load()
@@ -964,7 +973,8 @@ def pack_conv2d_weight(weight, cin_padded=None):
 def conv2d_block(x, packed_weight, cout, scale=None, shift=None, residual=None, stride=1,
                  relu=0, k=3, dilation=1, mode=None):
     """y = relu?(conv2d(x) * scale + shift (+ residual)) on NHWC maps, "same" padding.
-    ``x``: (B, Cin, H, W) in torch.channels_last memory, Cin a multiple of 16.  Inference only."""
+    ``x``: (B, Cin, H, W) in torch.channels_last memory, Cin a multiple of 16.  ``k`` = 5: stride 2 to 128 / 256
+    channels in the fp16 modes, no residual.  Inference only."""
     _require_device("conv2d_block", x, packed_weight, scale, shift, residual)
     if not x.is_contiguous(memory_format=_CL2D):
         x = carry_amax(x.contiguous(memory_format=_CL2D), x)
@@ -981,6 +991,23 @@ def conv2d_block(x, packed_weight, cout, scale=None, shift=None, residual=None, 
                  None if residual is None else (1, Ho, Wo), stride, False, relu,
                  2.0 * k * k * cin * cout * B * Ho * Wo, kd=1, k=k, dil=dilation, mode=mode)
     return y
+
+
+def conv2d_k5_plan_ok(B, cin, cout, Hi, Wi, mode=None):
+    """Does ``dsm_conv3d_plan`` admit Conv2d(cin -> cout, k5, pad 2, stride 2) on a (B, cin, Hi, Wi) map in
+    precision ``mode``?  The host-only query with stand-in addresses (only NULL-ness and alignment are looked
+    at): the geometry and offset limits are the library's, not a copy of them."""
+    mode = _mode(mode)
+    a = _lib.Conv3dArgs()
+    a.x = a.w_packed = a.y = a.x_amax = 16
+    a.B, a.Cin, a.Cout = int(B), int(cin), int(cout)
+    a.Di, a.Hi, a.Wi = 1, int(Hi), int(Wi)
+    a.Do, a.Ho, a.Wo = 1, (int(Hi) - 1) // 2 + 1, (int(Wi) - 1) // 2 + 1
+    a.stride, a.relu, a.kd, a.k, a.dil = 2, 1, 1, 5, 1
+    a.precision = {"f16x2": _lib.DSM_PREC_F16X2, "f16": _lib.DSM_PREC_F16}.get(mode, _lib.DSM_PREC_F32)
+    a.flags = _conv_flags(mode)
+    buf = ctypes.create_string_buffer(96)
+    return _lib.load().dsm_conv3d_plan(ctypes.byref(a), buf, 96) == _lib.DSM_OK
 
 
 def conv2d_transposed_block(x, packed_weight, cout, out_size, mode=None):

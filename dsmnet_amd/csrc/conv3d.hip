@@ -879,7 +879,13 @@ size_t bf16x3_section_bytes(int Cin, int Cout, int kd, int k) {
 bool wide2d_layer(int Cin, int Cout, int kd, int k) {
   return kd == 1 && k == 3 && Cin % 16 == 0 && (Cout == 256 || Cout == 512 || Cout == 1024);
 }
+// The 5x5 stride-2 layers (Cout 128 / 256; conv_wide2d.hpp with K = 5) carry section 3 ALONE: no fp32
+// fragments either, the layer has neither an fp32 nor a bf16x3 kernel.
+bool k5_layer(int Cin, int Cout, int kd, int k) {
+  return kd == 1 && k == 5 && Cin % 16 == 0 && (Cout == 128 || Cout == 256);
+}
 size_t f16_section_bytes(int Cin, int Cout, int kd, int k) {
+  if (k5_layer(Cin, Cout, kd, k)) return 16 + (size_t)Cin * Cout * 25 * 4;
   return (bf16x3_section_bytes(Cin, Cout, kd, k) || wide2d_layer(Cin, Cout, kd, k))
              ? 16 + (size_t)Cin * Cout * kd * 9 * 4 : 0;
 }
@@ -965,11 +971,22 @@ extern "C" int dsm_conv_pack_weights(const void* w_torch, void* w_packed, int Ci
                                      int Cout, int kd, int k, dsm_stream_t stream) {
   DSM_REQUIRE(w_torch && w_packed && w_torch != w_packed, DSM_ERR_ARG);
   DSM_REQUIRE(Cin_src > 0 && Cin >= Cin_src && Cout > 0, DSM_ERR_ARG);
-  DSM_REQUIRE((kd == 1 || kd == 3) && (k == 1 || k == 3), DSM_ERR_UNSUPPORTED);
+  DSM_REQUIRE(((kd == 1 || kd == 3) && (k == 1 || k == 3)) || k5_layer(Cin, Cout, kd, k), DSM_ERR_UNSUPPORTED);
   DSM_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0, DSM_ERR_UNSUPPORTED);
   const int ntaps = kd * k * k;
   const long n = (long)Cin * Cout * ntaps;
   dsm_clear_stale_error();
+  if (k == 5) {                                          // the fp16 section alone: header, two planes
+    char* const sec3 = (char*)w_packed;
+    if (hipMemsetAsync(sec3, 0, 16, (hipStream_t)stream) != hipSuccess) return DSM_ERR_LAUNCH;
+    const long nsrc = (long)Cin_src * Cout * ntaps, nb = dsm_cdiv(dsm_cdiv(nsrc, 4), 256);
+    hipLaunchKernelGGL(absmax_kernel, dim3(nb < 64 ? nb : 64), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)w_torch, nsrc, (float*)sec3);
+    hipLaunchKernelGGL(pack_weights_split_kernel<2>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)w_torch, (unsigned short*)(sec3 + 16), (const float*)sec3, Cin, Cout, 0, ntaps,
+                       Cin_src);
+    return dsm_launch_status();
+  }
   hipLaunchKernelGGL(pack_weights_kernel, dim3(dsm_cdiv(n, 256)), dim3(256), 0,
                      (hipStream_t)stream, (const float*)w_torch, (float*)w_packed, Cin, Cout, 0,
                      ntaps, Cin_src);
@@ -990,6 +1007,7 @@ extern "C" int dsm_absmax(const void* x, size_t n, float* amax, dsm_stream_t str
 
 extern "C" size_t dsm_conv_packed_weight_bytes(int Cin, int Cout, int kd, int k) {
   if (Cin <= 0 || Cout <= 0) return 0;
+  if (k5_layer(Cin, Cout, kd, k)) return f16_section_bytes(Cin, Cout, kd, k);
   if (!((kd == 1 || kd == 3) && (k == 1 || k == 3))) return 0;
   return (size_t)Cin * Cout * kd * k * k * sizeof(float) + bf16x3_section_bytes(Cin, Cout, kd, k) +
          f16_section_bytes(Cin, Cout, kd, k);
@@ -1000,7 +1018,9 @@ namespace {
 // Work decomposition of a wide 2-D layer (conv_wide2d.hpp), a pure function of the arguments: M-block,
 // N-column width (64, or 32 where 64-wide columns cannot give every CU a workgroup), K-ranges.
 // flags bits 8..13 force the number of K-ranges (clamped to the 16-channel chunks there are).
+// The 5x5 layers (kind 10) share it: their window is in a->k.
 bool wide2d_units(const dsm_conv3d_args* a, WideParams* w) {
+  w->K = a->k == 5 ? 5 : 3;
   w->B = a->B; w->Cin = a->Cin; w->Cout = a->Cout; w->Hi = a->Hi; w->Wi = a->Wi; w->Ho = a->Ho; w->Wo = a->Wo;
   w->S = a->transposed ? 1 : a->stride;              // transposed (kind 9): the stride-1 geometry over Ho x Wo
   if (!dsmk::wide2d_geometry(*w)) return false;
@@ -1036,6 +1056,22 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
               dsm_aligned16(a->y), DSM_ERR_ALIGN);
   DSM_REQUIRE(a->precision == DSM_PREC_F32 || a->precision == DSM_PREC_F16X2 || a->precision == DSM_PREC_F16, DSM_ERR_ARG);
   const int kd = a->kd ? a->kd : 3, k = a->k ? a->k : 3, dil = a->dil ? a->dil : 1;
+  if (k == 5) {
+    // the 5x5 stride-2 layers (DispNet conv2 / conv3a; conv2 of DispNetC / iResNet): conv_wide2d.hpp with
+    // K = 5, fp16 modes only, no skip input, the natural output size; 32-bit offsets with the out-of-range
+    // marker at 2^31.  (This check sits before the generic Cout 32 / 64 / 128 path: Cout = 128 is both.)
+    DSM_REQUIRE(k5_layer(a->Cin, a->Cout, kd, k) && dil == 1 && a->stride == 2 && !a->transposed &&
+                !a->vol_virtual && !a->residual && a->Di == 1 && a->Do == 1 &&
+                a->Ho == (a->Hi - 1) / 2 + 1 && a->Wo == (a->Wi - 1) / 2 + 1, DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(a->precision != DSM_PREC_F32 && bf16x3_enabled(a), DSM_ERR_UNSUPPORTED);
+    DSM_REQUIRE(4ul * a->B * a->Hi * a->Wi * a->Cin < 0x80000000ul &&
+                (unsigned long)a->B * a->Ho * a->Wo * a->Cout < 0x7fffffffUL, DSM_ERR_UNSUPPORTED);
+    WideParams w;
+    DSM_REQUIRE(wide2d_units(a, &w), DSM_ERR_UNSUPPORTED);
+    *pl = Plan{10, 2, w.nwn, w.nunits, 16, 1, 5, 1};     // (TM: the work units)
+    pl->nsplit = w.ksplit;
+    return DSM_OK;
+  }
   DSM_REQUIRE((kd == 1 || kd == 3) && (k == 1 || k == 3) && (dil == 1 || dil == 2),
               DSM_ERR_UNSUPPORTED);
   if (kd == 1 && a->transposed) {
@@ -1185,7 +1221,7 @@ fp32_kernels:
 int make_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
   const int rc = select_plan_f32(a, pl);
   if (rc != DSM_OK) return rc;
-  if (pl->kind != 7 && pl->kind != 8 && pl->kind != 9) { // 32-bit buffer offsets (kinds 7 / 8 / 9 bound theirs above)
+  if (pl->kind != 7 && pl->kind != 8 && pl->kind != 9 && pl->kind != 10) { // 32-bit buffer offsets (kinds 7 .. 10 bound theirs above)
     const int kd = a->kd ? a->kd : 3, k = a->k ? a->k : 3;
     DSM_REQUIRE(4ul * a->B * a->Di * a->Hi * a->Wi * a->Cin < (1ul << 32) &&
                 4ul * a->Cin * a->Cout * kd * k * k < (1ul << 32), DSM_ERR_UNSUPPORTED);
@@ -1198,7 +1234,7 @@ int make_plan(const dsm_conv3d_args* a, Plan* pl) {
   const int rc = make_plan_f32(a, pl);
   if (rc != DSM_OK) return rc;
   pl->pm = 3;
-  if ((pl->kind == 5 || pl->kind == 6 || pl->kind == 7 || pl->kind == 8 || pl->kind == 9) && a->precision != DSM_PREC_F32) {
+  if ((pl->kind == 5 || pl->kind == 6 || pl->kind == 7 || pl->kind == 8 || pl->kind == 9 || pl->kind == 10) && a->precision != DSM_PREC_F32) {
     DSM_REQUIRE(a->x_amax != nullptr, DSM_ERR_ARG);      // the input's absolute maximum (device scalar)
     pl->pm = a->precision == DSM_PREC_F16X2 ? 2 : 1;
   }
@@ -1237,6 +1273,7 @@ extern "C" int dsm_conv3d_plan(const dsm_conv3d_args* a, char* buf, int len) {
       break;
     }
     case 8: snprintf(buf, len, "conv2d_wide_%s_mfma_kernel<S=%d,N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", pl.S, 32 * pl.NT, pl.nsplit, pl.TM); break;
+    case 10: snprintf(buf, len, "conv2d_k5_%s_mfma_kernel<S=%d,N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", pl.S, 32 * pl.NT, pl.nsplit, pl.TM); break;
     case 9: snprintf(buf, len, "deconv2d_wide_%s_mfma_kernel<N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", 32 * pl.NT, pl.nsplit, pl.TM); break;
     case 7: snprintf(buf, len, "conv3d_zs_%s_mfma_kernel%s", pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), a->vol_virtual ? "<vol>" : ""); break;
     case 6: snprintf(buf, len, "deconv3d_%s%s_mfma_kernel<NT=%d>", pl.zs ? "zs_" : "",
@@ -1272,7 +1309,7 @@ extern "C" int dsm_basicblock2d_fwd(const dsm_basicblock2d_args* a, dsm_stream_t
 
 extern "C" size_t dsm_conv3d_workspace_bytes(const dsm_conv3d_args* a) {
   Plan pl;
-  if (make_plan_f32(a, &pl) != DSM_OK || (pl.kind != 8 && pl.kind != 9) || pl.nsplit <= 1) return 0;
+  if (make_plan_f32(a, &pl) != DSM_OK || (pl.kind != 8 && pl.kind != 9 && pl.kind != 10) || pl.nsplit <= 1) return 0;
   return (size_t)pl.nsplit * a->B * a->Ho * a->Wo * a->Cout * sizeof(float);
 }
 
@@ -1280,22 +1317,25 @@ extern "C" int dsm_conv3d_fwd(const dsm_conv3d_args* a, dsm_stream_t stream) {
   Plan pl;
   int rc = make_plan(a, &pl);
   if (rc != DSM_OK) return rc;
-  if (pl.kind == 8 || pl.kind == 9) {
+  if (pl.kind == 8 || pl.kind == 9 || pl.kind == 10) {
     WideParams w;
     wide2d_units(a, &w);
     const size_t need = dsm_conv3d_workspace_bytes(a);
     DSM_REQUIRE(need == 0 || (a->workspace && a->workspace_bytes >= need), DSM_ERR_ARG);
     DSM_REQUIRE(need == 0 || dsm_aligned16(a->workspace), DSM_ERR_ALIGN);
     DSM_REQUIRE(a->relu == 0 || a->relu == 1 || a->relu == 2, DSM_ERR_ARG);
-    const char* sec3 = (const char*)a->w_packed + (size_t)a->Cin * a->Cout * 9 * 4;
+    const int ntaps = pl.kind == 10 ? 25 : 9;
+    // (a 5x5 layer's packed buffer IS its fp16 section; a 3x3 layer's section lies behind the fp32 fragments)
+    const char* sec3 = (const char*)a->w_packed + (pl.kind == 10 ? 0 : (size_t)a->Cin * a->Cout * 9 * 4);
     w.x = (const float*)a->x; w.w = (const unsigned char*)(sec3 + 16); w.w_amax = (const float*)sec3;
     w.scale = a->scale; w.shift = a->shift; w.y = (float*)a->y; w.ws = (float*)a->workspace;
     w.x_amax = a->x_amax; w.y_amax = a->y_amax; w.relu = a->relu ? 1 : 0;
     w.xbytes = (unsigned)(4ul * a->B * a->Hi * a->Wi * a->Cin);
-    w.wbytes = (unsigned)((size_t)a->Cin * a->Cout * 9 * 4);
+    w.wbytes = (unsigned)((size_t)a->Cin * a->Cout * ntaps * 4);
     int grid = (a->flags >> DSM_CONV_BLOCKS_SHIFT) & 0xffff;      // forced grid: the units are walked in a loop
     if (grid <= 0 || grid > w.nunits) grid = w.nunits;
     dsm_clear_stale_error();
+    if (pl.kind == 10) return dsmk::run_conv2d_k5_f16(pl.pm, w, grid, (hipStream_t)stream);
     return dsmk::run_wide2d_f16(pl.pm, w, grid, pl.kind == 9, (hipStream_t)stream);
   }
   ConvParams p;

@@ -26,7 +26,8 @@ struct ConvParams {
 // One place decides the kernel variant; dsm_conv3d_fwd launches it, dsm_conv3d_plan names it.
 // kind: 0 conv, 1 deconv, 2 conv cout1, 3 deconv cout1, 4 conv cout1 z-sliding, 5 conv split (bf16x3 / f16x2 / f16), 6 deconv split,
 //       7 z-sliding conv (Cout = 32, stride 1; conv_zs.hpp), 8 wide 2-D conv (Cout 256 / 512 / 1024; conv_wide2d.hpp),
-//       9 its transposed mode (stride 2; backward-data of the stride-2 wide layers)
+//       9 its transposed mode (stride 2; backward-data of the stride-2 wide layers),
+//       10 the 5x5 stride-2 2-D conv (Cout 128 / 256; conv_wide2d.hpp with K = 5, fp16 modes only)
 // zs (kind 6, fp16 modes): the z-sliding transposed convolution (deconv_zs.hpp) instead of deconv_split_kernel
 struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int pm = 3; int once = 0; int zs = 0; };
 
@@ -50,7 +51,7 @@ struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int p
   X(1, 4, 1, 1, 1) X(1, 2, 1, 1, 1) X(2, 2, 1, 1, 1) X(2, 1, 1, 1, 1) X(4, 2, 1, 1, 1) X(4, 2, 1, 2, 1) \
   X(1, 2, 1, 1, 2) X(2, 2, 1, 1, 2) X(1, 1, 3, 1, 2) X(1, 1, 3, 1, 4)
 
-// Is the kernel variant that `pl` selects compiled?  (Kinds 2, 3, 4, 7, 8, 9 are single kernels.)
+// Is the kernel variant that `pl` selects compiled?  (Kinds 2, 3, 4, 7, 8, 9, 10 are single kernels.)
 inline bool plan_compiled(const Plan& pl) {
   switch (pl.kind) {
     case 0:
@@ -126,7 +127,8 @@ struct BbParams {
 
 __attribute__((visibility("hidden"))) int run_basicblock_f16(int pm, const BbParams& p, hipStream_t s);
 
-// the wide 2-D convolution (conv_wide2d.hpp, plan kind 8): Cout = 256 | 512 | 1024, fp16 modes
+// the wide 2-D convolution (conv_wide2d.hpp, plan kind 8): Cout = 256 | 512 | 1024, fp16 modes; with a 5x5
+// window at stride 2 (plan kind 10): Cout = 128 | 256
 constexpr int WIDE_SLOTS = 768;     // LDS voxel slots of one staged input box
 constexpr int WIDE_PIXELS = 512;    // output pixels of an M-block: 8 waves x 4 M-tiles of 32 / 2 output blocks
 struct WideParams {
@@ -142,17 +144,19 @@ struct WideParams {
   int nwn, ncol;                // 32-channel output blocks per workgroup (2 | 1), N-columns = Cout / (32 nwn)
   int ksplit, nunits;
   unsigned xbytes, wbytes;
+  int K = 3;                    // window (host side: the geometry; the kernel has it as a template argument)
 };
 // M-block of a layer: the (R, CW) with the fewest rounds of M-tiles (a round = one M-tile on each of four
 // wave groups), then the fewest blocks, among column splits nbx = 1 .. 8.  False: no block fits.
+// The box of a block is ((R-1) S + K) x ((CW-1) S + K) voxels for a K x K window.
 inline bool wide2d_geometry(WideParams& p) {
   long best = -1;
   for (int nbx = 1; nbx <= 8; ++nbx) {
     const int CW = (p.Wo + nbx - 1) / nbx;
-    const int IX = (CW - 1) * p.S + 3, XE = (IX + 1) / 2, XP = p.S == 1 ? IX : 2 * XE;
-    if (CW > WIDE_PIXELS || 3 * XP > WIDE_SLOTS) continue;
+    const int IX = (CW - 1) * p.S + p.K, XE = (IX + 1) / 2, XP = p.S == 1 ? IX : 2 * XE;
+    if (CW > WIDE_PIXELS || p.K * XP > WIDE_SLOTS) continue;
     int R = WIDE_PIXELS / CW;
-    const int rl = (WIDE_SLOTS / XP - 3) / p.S + 1;
+    const int rl = (WIDE_SLOTS / XP - p.K) / p.S + 1;
     if (rl < R) R = rl;
     if (p.Ho < R) R = p.Ho;
     const int nby = (p.Ho + R - 1) / R;
@@ -162,12 +166,13 @@ inline bool wide2d_geometry(WideParams& p) {
     if (best < 0 || cost < best) {
       best = cost;
       p.R = R; p.CW = CW; p.nbx = nbx; p.nby = nby;
-      p.IY = (R - 1) * p.S + 3; p.IX = IX; p.XP = XP; p.XE = XE;
+      p.IY = (R - 1) * p.S + p.K; p.IX = IX; p.XP = XP; p.XE = XE;
     }
   }
   return best >= 0;
 }
 __attribute__((visibility("hidden"))) int run_wide2d_f16(int pm, const WideParams& p, int grid, int transposed, hipStream_t s);
+__attribute__((visibility("hidden"))) int run_conv2d_k5_f16(int pm, const WideParams& p, int grid, hipStream_t s);
 
 }  // namespace dsmk
 

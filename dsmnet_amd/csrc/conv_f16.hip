@@ -6,7 +6,8 @@
 //          config #5 ("PSMNet fp16 training step"); the reference itself computes in fp32
 //          (models/psmnet/stackhourglass.py:124).
 // Also here: the wide 2-D layers of the DispNetC / iResNet encoder (conv_wide2d.hpp: Cout 256 / 512 / 1024,
-// models/dispnetcorr.py conv3b .. conv6b), which exist in the fp16 modes only.
+// models/dispnetcorr.py conv3b .. conv6b), which exist in the fp16 modes only, and the same kernel with a 5x5
+// window at stride 2 (models/dispnet.py conv2 / conv3a; the conv2 of DispNetC and iResNet).
 // Replaces the same reference code as conv3d.hip: convbn_3d / conv3d_bn / deconv3d_bn and the
 // towers' convbn (models/psmnet/submodule.py:10-19, stackhourglass.py:22-62,73-98,135-149,
 // models/util_conv.py:150-179).
@@ -47,5 +48,11 @@ int dsmk::run_wide2d_f16(int pm, const WideParams& p, int grid, int transposed, 
   }
   if (pm == 2) return launch_conv_wide2d<2>(p, grid, s);
   if (pm == 1) return launch_conv_wide2d<1>(p, grid, s);
+  return DSM_ERR_UNSUPPORTED;
+}
+
+int dsmk::run_conv2d_k5_f16(int pm, const WideParams& p, int grid, hipStream_t s) {
+  if (pm == 2) return launch_conv_wide2d<2, false, 5>(p, grid, s);
+  if (pm == 1) return launch_conv_wide2d<1, false, 5>(p, grid, s);
   return DSM_ERR_UNSUPPORTED;
 }

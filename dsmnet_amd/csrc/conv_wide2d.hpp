@@ -2,6 +2,8 @@
 // DispNetC / iResNet encoders (models/dispnetcorr.py conv3b .. conv6b, models/iresnet.py conv3_1 .. conv6_1;
 // models/util_conv.py conv2d_bn with bn = False), fp32 NHWC in and out, in the fp16 modes (PM = 2 "f16x2",
 // PM = 1 "f16").  Included by conv_f16.hip after conv_split.hpp.
+// With the window as a template argument (K = 5) also Conv2d(Cin -> 128 | 256, k5, pad 2, stride 2) + bias + ReLU:
+// conv2 / conv3a of DispNet (models/dispnet.py) and the conv2 of DispNetC / iResNet -- see the note at the kernel.
 //
 // The regime is the opposite of the towers': small M (120 .. 7,680 output pixels per pair), large N (Cout)
 // and K (9 Cin up to 9,216) -- the time is weight streaming (up to 37.7 MB of fp16 planes per layer) and
@@ -26,10 +28,11 @@
 // [voxel slot][plane NP][16 ch], pitch (2 NP + 1) x 16 B -- an odd number of 16-byte units, conflict-free
 // ds_read_b128 for lanes on consecutive slots; stride 2 keeps even and odd input columns of a row apart
 // (row pitch XP = 2 XE) so that lanes stepping two input columns still sit on consecutive slots.  Per tap:
-// one weight fragment per wave (buffer loads, ring of three, running on across chunks) feeds up to four
+// one weight fragment per wave (buffer loads, ring of three -- five for the 5x5 window --, running on across
+// chunks) feeds up to four
 // M-tiles' product groups; each lane reads ITS pixel's fragment (the M-tiles are runs of the linearised
 // block, not image rows).  One barrier per chunk.
-// Weights: the packed f16 section of dsm_conv_pack_weights, [Cin/16][tap9][Cout/32][plane 2][lane][16 B].
+// Weights: the packed f16 section of dsm_conv_pack_weights, [Cin/16][tap 9 | 25][Cout/32][plane 2][lane][16 B].
 #pragma once
 
 template <int PM>
@@ -48,12 +51,21 @@ struct WideCfg {
 // kernel over the Ho x Wo map X' with X'[2i][2j] = x[i][j] and zeros elsewhere (p.S = 1, p.Hi x p.Wi the
 // extent of x itself): only the staging address differs -- a slot whose ABSOLUTE coordinate is even in both
 // directions loads x[y/2][x/2], every other slot takes the out-of-range offset.
-template <int PM, bool TR = false>
+//
+// K: the window (3, or 5 for plan kind 10: Conv2d(k5, pad 2, stride 2) + bias + ReLU of DispNet's conv2 / conv3a
+// and the conv2 of DispNetC / iResNet).  Everything above holds with 25 taps per chunk, a box of
+// ((R-1) S + 5) x ((CW-1) S + 5) voxels and the tap's column split (kx & 1, kx >> 1) over the even / odd halves
+// of a row; the weights are the same section with 25 taps, [Cin/16][tap25][Cout/32][plane 2][lane][16 B].
+template <int PM, bool TR = false, int K = 3>
 __global__ __launch_bounds__(512, 2) void conv_wide2d_kernel(WideParams p) {
+  static_assert(K == 3 || (K == 5 && !TR), "windows: 3x3, or 5x5 forward");
+  constexpr int KK = K * K, PAD = (K - 1) / 2;
   using Cf = WideCfg<PM>;
   using frag = typename Prec<PM>::frag;
   constexpr int NP = Cf::NP, NPW = Cf::NPW, NPF = Cf::NPF, PITCH = Cf::PITCH, IMG = Cf::IMG;
-  constexpr int AHEAD = 3, MT = 4;
+  // the weight ring runs on across chunks, so its length divides the taps of a chunk (9 = 3 x 3, 25 = 5 x 5)
+  constexpr int AHEAD = K == 5 ? 5 : 3, MT = 4;
+  static_assert(KK % AHEAD == 0, "the ring's slot of a tap must not depend on the chunk");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   float* const red = reinterpret_cast<float*>(lds_raw + 2 * IMG);
 
@@ -68,12 +80,12 @@ __global__ __launch_bounds__(512, 2) void conv_wide2d_kernel(WideParams p) {
   const float sx = ss.sx, so = ss.out;
   const __amdgpu_buffer_rsrc_t xrs = make_rsrc(p.x, p.xbytes), wrs = make_rsrc(p.w, p.wbytes);
   const unsigned WTAP = (unsigned)NT * NPW * 1024u;    // weight bytes per (chunk, tap)
-  const unsigned WCH = 9u * WTAP;
+  const unsigned WCH = (unsigned)KK * WTAP;
 
-  int tapoff[9];                                       // LDS bytes from a pixel's tap (0, 0) voxel
+  int tapoff[KK];                                      // LDS bytes from a pixel's tap (0, 0) voxel
 #pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int ky = t / 3, kx = t % 3;
+  for (int t = 0; t < KK; ++t) {
+    const int ky = t / K, kx = t % K;
     tapoff[t] = (ky * p.XP + (p.S == 2 ? (kx & 1) * p.XE + (kx >> 1) : kx)) * PITCH;
   }
   const int npx = p.R * p.CW, ntile = (npx + 31) >> 5;
@@ -99,7 +111,7 @@ __global__ __launch_bounds__(512, 2) void conv_wide2d_kernel(WideParams p) {
       const int slot = e >> 2, q = e & 3;
       const int yy = slot / p.XP, xs = slot % p.XP;
       const int xx = p.S == 2 ? (xs < p.XE ? 2 * xs : 2 * (xs - p.XE) + 1) : xs;
-      const int y = y0 * p.S - 1 + yy, x = x0 * p.S - 1 + xx;
+      const int y = y0 * p.S - PAD + yy, x = x0 * p.S - PAD + xx;
       if constexpr (TR) {
         const bool ok = yy < p.IY && xx < p.IX && y >= 0 && x >= 0 && !((y | x) & 1) && (y >> 1) < p.Hi && (x >> 1) < p.Wi;
         voff[k] = ok ? (unsigned)(4l * ((((long)b * p.Hi + (y >> 1)) * p.Wi + (x >> 1)) * p.Cin + 4 * q)) : OOBV;
@@ -165,10 +177,10 @@ __global__ __launch_bounds__(512, 2) void conv_wide2d_kernel(WideParams p) {
       const unsigned char* const img = lds_raw + ((c - c0) & 1) * IMG;
       const bool more = c + 1 < c1;                    // uniform
       if (more) gload(c + 1);
-      static_for<0, 9>([&](auto ic) {
+      static_for<0, KK>([&](auto ic) {
         constexpr int item = decltype(ic)::value;
-        if constexpr (item + AHEAD - 1 < 9) wload(std::integral_constant<int, item + AHEAD - 1>{}, c);
-        else if (more) wload(std::integral_constant<int, item + AHEAD - 1 - 9>{}, c + 1);
+        if constexpr (item + AHEAD - 1 < KK) wload(std::integral_constant<int, item + AHEAD - 1>{}, c);
+        else if (more) wload(std::integral_constant<int, item + AHEAD - 1 - KK>{}, c + 1);
         frag xq[MT][NP];
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -235,11 +247,11 @@ __global__ __launch_bounds__(256) void wide2d_reduce_kernel(WideParams p) {
   publish_amax<4>(p.y_amax, am, red);
 }
 
-template <int PM, bool TR = false>
+template <int PM, bool TR = false, int K = 3>
 int launch_conv_wide2d(const WideParams& p, int grid, hipStream_t s) {
   using Cf = WideCfg<PM>;
-  DSM_REQUIRE((dsm_allow_lds<conv_wide2d_kernel<PM, TR>>(Cf::LDS) == DSM_OK), DSM_ERR_LAUNCH);
-  hipLaunchKernelGGL((conv_wide2d_kernel<PM, TR>), dim3((unsigned)grid), dim3(Cf::THREADS), Cf::LDS, s, p);
+  DSM_REQUIRE((dsm_allow_lds<conv_wide2d_kernel<PM, TR, K>>(Cf::LDS) == DSM_OK), DSM_ERR_LAUNCH);
+  hipLaunchKernelGGL((conv_wide2d_kernel<PM, TR, K>), dim3((unsigned)grid), dim3(Cf::THREADS), Cf::LDS, s, p);
   if (p.ksplit > 1) {
     const long nq = (long)p.B * p.Ho * p.Wo * (p.Cout >> 2);
     const long blocks = dsm_cdiv(nq, 256);

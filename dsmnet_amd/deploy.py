@@ -132,7 +132,7 @@ def main(argv=None):
     from .models import model_create_by_name
     ap = argparse.ArgumentParser(description="stereo matching, single pair (MI355X)")
     ap.add_argument("--net", default="dispnetcorr", type=str,
-                    help="dispnetcorr / iresnet / gcnet / psmnet")
+                    help="dispnet / dispnetcorr / iresnet / gcnet / psmnet")
     ap.add_argument("--maxdisparity", default=192, type=int)
     ap.add_argument("--path_weight", default="", type=str)
     ap.add_argument("--path_left", default="10L.png", type=str)

@@ -5,7 +5,8 @@ cost-volume path runs.
   conv3d_bn / deconv3d_bn     -> blocks3d.ConvBN3d, one launch (util_conv.py:150-179)
   conv2d_bn(bn=False)         -> Conv2dReLU: Sequential(Conv2d, ReLU) whose wide 3x3 layers (256 / 512 /
       1024 outputs: the DispNetC / iResNet encoders) run on the wide MFMA kernel in eval mode
-      (csrc/conv_wide2d.hpp; ``costvolume`` option ``wide_conv2d``)
+      (csrc/conv_wide2d.hpp; ``costvolume`` option ``wide_conv2d``), and whose 5x5 stride-2 layers to 128 / 256
+      channels run on the same kernel with a 5x5 window (option ``conv2d_k5``)
   deconv2d_bn / conv_res / net_init -- 2-D layers outside the hot path: stock
       torch modules in the same Sequential layout (state-dict keys match the reference).
 """
@@ -67,8 +68,10 @@ class Conv2dReLU(nn.Sequential):
     convolution + bias + ReLU as one op on the wide MFMA kernel (NHWC in and out, the output carries
     its absolute maximum for the next layer).  Under autograd with the option ``wide_conv2d_train`` on, the
     layers with Cin and Cout both in 256 / 512 / 1024 run ``costvolume.wide_conv2d_relu`` (explicit gradients on
-    the HIP kernels, NHWC).  Everything else -- CPU tensors, k 5 / 7, odd Cin, the narrower layers, training
-    with that option off -- runs the two children as before."""
+    the HIP kernels, NHWC).  With the option ``conv2d_k5`` on (eval mode, no autograd, fp32 on the GPU, an fp16
+    precision mode, nn.ReLU) a layer ``blocks2d.k5_ok`` admits -- k5, pad 2, stride 2, Cin % 16 == 0, 128 / 256
+    outputs -- is one op on the 5x5 form of that kernel in the same way.  Everything else -- CPU tensors, k 7,
+    odd Cin, the narrower 3x3 layers, training with those options off -- runs the two children as before."""
 
     def __init__(self, conv, act):
         super(Conv2dReLU, self).__init__(conv, act)
@@ -89,6 +92,15 @@ class Conv2dReLU(nn.Sequential):
                 if self._folded is None:
                     self._folded = _Folded2d()
                 return run_conv2d(self._folded, conv, None, x, relu=True)
+        if (not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and
+                conv.kernel_size == (5, 5) and cv.get_option("conv2d_k5") and cv.needs_amax() and
+                isinstance(self[1], nn.ReLU)):
+            from ..blocks2d import _Folded2d, k5_ok
+            if k5_ok(conv, x):
+                if self._folded is None:
+                    self._folded = _Folded2d()
+                packed, scale, shift = self._folded.get(conv, None, x.shape[1])
+                return cv.conv2d_block(x, packed, conv.out_channels, scale, shift, stride=2, relu=1, k=5)
         return super(Conv2dReLU, self).forward(x)
 
     def __deepcopy__(self, memo):

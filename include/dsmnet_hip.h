@@ -240,7 +240,7 @@ typedef struct dsm_conv3d_args {
    * k in {1,3}, dil in {1,2}, padding = dil*(k-1)/2 ("same"), as in convbn()
    * (models/psmnet/submodule.py:10-13) for k = 3 and the towers' 1x1 convolutions. */
   int kd;                 /* depth taps: 3 (default) or 1            */
-  int k;                  /* taps in y and x: 3 (default) or 1       */
+  int k;                  /* taps in y and x: 3 (default) or 1; 5: see "5x5 stride-2 layers" below */
   int dil;                /* dilation in y and x: 1 (default) or 2   */
   /* ABI v4: tuning / A-B switches of THIS call (0 = the plan's own choice).  The library reads no
    * environment variable and holds no global switch: a plan is a pure function of the arguments. */
@@ -286,7 +286,7 @@ typedef struct dsm_conv3d_args {
 #define DSM_CONV_COUT1_CHUNKED  0x2      /* Cout = 1: the chunked kernel instead of the z-sliding one */
 #define DSM_CONV_NO_NSPLIT      0x4      /* 2-D bf16x3 layers: one workgroup per tile (no N-split)    */
 #define DSM_CONV_NO_ONCE        0x8      /* A/B: the chunk-pipelined single-kind kernels instead of the single-tile (2-D 64 -> 64) and two-kind (stride-2 3-D) forms */
-#define DSM_CONV_KSPLIT_SHIFT   8        /* bits 8..13: wide 2-D layers: force the number of K-ranges (1..63, clamped to [ceil(Cin / 128), Cin / 16]) */
+#define DSM_CONV_KSPLIT_SHIFT   8        /* bits 8..13: wide 2-D and 5x5 stride-2 layers: force the number of K-ranges (1..63, clamped to [ceil(Cin / 128), Cin / 16]) */
 #define DSM_CONV_TM_SHIFT       4        /* bits 4..7: force the tile height 4*TM rows (TM = 1, 2, 4) */
 #define DSM_CONV_BLOCKS_SHIFT   16       /* bits 16..31: force the persistent grid size               */
 
@@ -301,7 +301,9 @@ int dsm_conv3d_pack_weights(const void* w_torch, void* w_packed,
  * Cin_src..Cin-1 are packed as zeros (PSMNet's first convolution: 3 staged as 16).
  * Bytes needed: dsm_conv_packed_weight_bytes (the fp32 fragments, Cin*Cout*kd*k*k*4, followed for
  * 3x3(x3) kernels by the pre-split bf16 planes the bf16x3 kernels read and by the two fp16 planes
- * of the power-of-two-scaled weights behind a 16-byte header holding their absolute maximum). */
+ * of the power-of-two-scaled weights behind a 16-byte header holding their absolute maximum).
+ * kd = 1, k = 5 (Cout 128 | 256, Cin % 16 == 0; every other 5x5 shape: 0 bytes, DSM_ERR_UNSUPPORTED): the
+ * header and the two fp16 planes ALONE, 16 + Cin*Cout*25*4 bytes. */
 size_t dsm_conv_packed_weight_bytes(int Cin, int Cout, int kd, int k);
 int dsm_conv_pack_weights(const void* w_torch, void* w_packed, int Cin_src, int Cin, int Cout,
                           int kd, int k, dsm_stream_t stream);
@@ -340,7 +342,19 @@ int dsm_conv3d_fwd(const dsm_conv3d_args* args, dsm_stream_t stream);
  * each per (pixel block, N = 64 | 32 output channels); K > 1: the partial sums meet in `workspace`
  * ([K][B*Ho*Wo][Cout] floats) and a second launch adds them in index order (no float atomics: the
  * result is bit-identical from run to run; different K differ in the low bits).  This query: the bytes
- * `workspace` must hold for `args` (flags included); 0 when the layer needs none or is not such a layer. */
+ * `workspace` must hold for `args` (flags included); 0 when the layer needs none or is not such a layer.
+ *
+ * (ABI v7, additive) 5x5 stride-2 layers -- Conv2d(k5, pad 2, stride 2) to Cout = 128 | 256 from Cin % 16 == 0
+ * (kd = 1, k = 5, stride = 2, dil = 1, no residual, the natural output size Ho = (Hi - 1) / 2 + 1), conv2 and
+ * conv3a of DispNet (models/dispnet.py:26-27) and the conv2 of DispNetC / iResNet -- run on
+ * "conv2d_k5_<f16x2|f16>_mfma_kernel<S=2,N,KS=K,units>", the same kernel with a 5x5 window: the same
+ * precisions (DSM_PREC_F32, or DSM_CONV_FP32_MFMA: DSM_ERR_UNSUPPORTED), the same K ranges, `workspace`
+ * rule, deterministic second launch and `flags` bits, x_amax required (DSM_ERR_ARG without), y_amax folded
+ * in.  Stride 1, dilation 2, other Cout, a residual, a cropped output, an output wider than 592 columns
+ * (eight column blocks of one staged box) and maps past the 32-bit offsets are DSM_ERR_UNSUPPORTED.
+ * w_packed: dsm_conv_pack_weights(..., kd = 1, k = 5), dsm_conv_packed_weight_bytes(Cin, Cout, 1, 5) =
+ * 16 + Cin * Cout * 25 * 4 bytes -- a 16-byte header {max |w|, 0, 0, 0} and the two fp16 planes
+ * [Cin/16][tap 25][Cout/32][plane][lane][16 B]; these layers have no fp32 and no bf16 section. */
 size_t dsm_conv3d_workspace_bytes(const dsm_conv3d_args* args);
 
 /* Name of the kernel variant dsm_conv3d_fwd would launch for `args` (tile shape and
