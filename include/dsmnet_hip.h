@@ -219,7 +219,10 @@ int dsm_soft_argmin_bwd_plan(const void* cost, const void* disp, const void* sta
  * transposed = 1: ConvTranspose3d(k=3, stride=2, padding=1, output_padding=1)
  * Activations are DSM_NDHWC, fp32.  (Do,Ho,Wo) may be smaller than the natural
  * output size: only that corner is computed -- this is the crop of myadd_3d.
- * Contraction runs on v_mfma_f32_32x32x2_f32 (exact fp32 products and sums).
+ * The contraction runs in the mode `precision` names (DSM_PREC_* below): split 16-bit operands on the bf16 /
+ * fp16 MFMAs with fp32 accumulation, or -- DSM_CONV_FP32_MFMA, and every layer no split kernel covers -- fp32
+ * operands on v_mfma_f32_32x32x2_f32.  Products are exact only in that last form; sums are rounded to fp32
+ * after every MFMA in all of them.
  * ------------------------------------------------------------------------- */
 typedef struct dsm_conv3d_args {
   const void*  x;         /* (B,Di,Hi,Wi,Cin)                                   */
@@ -280,7 +283,13 @@ typedef struct dsm_conv3d_args {
 #define DSM_PREC_F16    1
 /* fp32 accuracy on the fp16 pipe: x * 2^e = hi + lo in fp16 (22 significand bits), three MFMAs per
  * product (wl xh + wh xl + wh xh), fp32 accumulate; measured error vs float64 at or below the
- * bf16x3 and fp32-input kernels' (scripts/precision_check.py). */
+ * bf16x3 and fp32-input kernels' (scripts/precision_check.py).
+ * Supported range: a tensor's maximum (x_amax, max |w|) in [2^-48, 2^76) -- below it the exponent's clamp
+ * (+-60) leaves the scaled values short of 2^12 and bits are lost, from 2^76 the scaled maximum overflows fp16.
+ * Accuracy is relative to that maximum, not to each element: an operand element carries an absolute error of
+ * up to 2^-37 of its tensor's maximum (half an fp16 subnormal step against a maximum scaled to 2^12), so it
+ * keeps 22 bits only down to about 2^-14 of the maximum (tests/split_bound.py states the per-output bound,
+ * tests/test_split_contract_gpu.py holds every kernel to it). */
 #define DSM_PREC_F16X2  2
 #define DSM_CONV_FP32_MFMA      0x1      /* keep the layer on the exact fp32-input MFMA (no bf16x3)   */
 #define DSM_CONV_COUT1_CHUNKED  0x2      /* Cout = 1: the chunked kernel instead of the z-sliding one */
