@@ -80,6 +80,7 @@ def _wide_ok(conv, x):
     """The wide 3x3 layers (256 / 512 / 1024 outputs; csrc/conv_wide2d.hpp, plan kind 8 of
     ``dsm_conv3d_fwd``): k3, dilation 1, stride 1 or 2, Cin % 16 == 0, an fp16 precision mode (under
     "bf16x3" / "fp32" the plan refuses and the caller keeps the stock layer), 32-bit offsets."""
+    # own arithmetic on purpose: STRICTER than the plan (pixels, not M-blocks); a plan query would admit new shapes
     if conv.kernel_size[0] != 3 or conv.dilation[0] != 1 or cv.get_option("conv_precision") not in ("f16x2", "f16"):
         return False
     B, cin, H, W = x.shape

@@ -16,6 +16,7 @@ Reference code each op replaces (sunshinnnn/DSMnet):
   supervised_pyramid_loss   losses/loss.py:326-338, 407-421, stereo.py:103-113
 """
 import ctypes
+import functools
 import os
 import weakref
 
@@ -503,6 +504,18 @@ def conv3d_plan_name(args):
     return _plan_name("dsm_conv3d_plan", args)
 
 
+def _conv_plan(args):
+    """(rc, name) of ``dsm_conv3d_plan`` for a COPY of ``args`` in which every null one of ``x``, ``w_packed``, ``y``,
+    ``x_amax`` is a stand-in aligned address (only NULL-ness and alignment are looked at): needs no tensors."""
+    a = _lib.Conv3dArgs.from_buffer_copy(args)
+    for field in ("x", "w_packed", "y", "x_amax"):
+        if not getattr(a, field):
+            setattr(a, field, 16)
+    buf = ctypes.create_string_buffer(96)
+    rc = _lib.load().dsm_conv3d_plan(ctypes.byref(a), buf, 96)
+    return rc, buf.value.decode()
+
+
 # ----------------------------------------------------------------------------
 # host-side options, absolute maxima of the fp16 precisions, the virtual cost volume
 # ----------------------------------------------------------------------------
@@ -778,24 +791,10 @@ K5_COUT = (128, 256)            # the 5x5 stride-2 layers (plan kind 10)
 
 
 def _split_kernel_layer(a):
-    """Does ``dsm_conv3d_fwd`` run this layer on a split-operand kernel (conv3d.hip make_plan kinds
-    5 / 6)?  3x3(x3) taps, Cin % 16 == 0, Cout a multiple of 32 up to 64 (3-D; 128 on small volumes at
-    stride 1) / 128 (2-D); stride 1, 3-D stride 2 to 64 channels, or transposed from Cin % 32 == 0."""
-    kd, k = (a.kd or 3), (a.k or 3)
-    if kd == 1 and k == 5 and a.Cin % 16 == 0 and a.Cout in K5_COUT:           # the same kernel, 5x5 (plan kind 10)
-        return (a.dil or 1) == 1 and not a.transposed and a.stride == 2
-    if kd == 1 and k == 3 and a.Cin % 16 == 0 and a.Cout in WIDE2D_COUT:       # conv_wide2d.hpp (plan kinds 8, 9)
-        return (a.dil or 1) == 1 and (not a.transposed or a.stride == 2)
-    if k != 3 or a.Cin % 16 or a.Cout % 32 or a.Cout > 128:
-        return False
-    if kd == 3 and a.Cout == 128:                    # four workgroup columns of 32: small volumes, stride 1 only
-        tiles4 = a.B * a.Do * ((a.Ho + 3) // 4) * ((a.Wo + 31) // 32)
-        return (not a.transposed) and a.stride == 1 and (a.dil or 1) == 1 and tiles4 <= 128
-    if kd == 3 and a.Cout > 64:
-        return False
-    if a.transposed:
-        return kd == 3 and a.Cin % 32 == 0
-    return a.stride == 1 or (kd == 3 and a.Cout == 64)
+    """Does ``dsm_conv3d_fwd`` run ``a`` (precision and flags set) on a kernel that reads ``x_amax``?  The planner's
+    own answer: such a plan carries its mode in its name (include/dsmnet_hip.h).  False for a refused plan."""
+    rc, name = _conv_plan(a)
+    return rc == _lib.DSM_OK and ("_f16x2_" in name or "_f16_" in name)
 
 
 def _set_precision(a, x, y, mode=None):
@@ -994,20 +993,21 @@ def conv2d_block(x, packed_weight, cout, scale=None, shift=None, residual=None, 
 
 
 def conv2d_k5_plan_ok(B, cin, cout, Hi, Wi, mode=None):
-    """Does ``dsm_conv3d_plan`` admit Conv2d(cin -> cout, k5, pad 2, stride 2) on a (B, cin, Hi, Wi) map in
-    precision ``mode``?  The host-only query with stand-in addresses (only NULL-ness and alignment are looked
-    at): the geometry and offset limits are the library's, not a copy of them."""
-    mode = _mode(mode)
+    """Does ``dsm_conv3d_plan`` admit Conv2d(cin -> cout, k5, pad 2, stride 2) on a (B, cin, Hi, Wi) map in precision
+    ``mode``?  The host-only query: the geometry and offset limits are the library's, not a copy of them."""
+    return _conv_plan(_conv2d_standin(B, cin, cout, Hi, Wi, 2, 5, 1, _mode(mode), _conv_flags(mode)))[0] == _lib.DSM_OK
+
+
+def _conv2d_standin(B, cin, cout, Hi, Wi, stride, k, dil, mode, flags):
+    """``dsm_conv3d_args`` of Conv2d(cin -> cout, k, "same" padding) on a (B, cin, Hi, Wi) map, for ``_conv_plan``."""
     a = _lib.Conv3dArgs()
-    a.x = a.w_packed = a.y = a.x_amax = 16
     a.B, a.Cin, a.Cout = int(B), int(cin), int(cout)
     a.Di, a.Hi, a.Wi = 1, int(Hi), int(Wi)
-    a.Do, a.Ho, a.Wo = 1, (int(Hi) - 1) // 2 + 1, (int(Wi) - 1) // 2 + 1
-    a.stride, a.relu, a.kd, a.k, a.dil = 2, 1, 1, 5, 1
+    a.Do, a.Ho, a.Wo = 1, (int(Hi) - 1) // stride + 1, (int(Wi) - 1) // stride + 1
+    a.stride, a.relu, a.kd, a.k, a.dil = int(stride), 1, 1, int(k), int(dil)
     a.precision = {"f16x2": _lib.DSM_PREC_F16X2, "f16": _lib.DSM_PREC_F16}.get(mode, _lib.DSM_PREC_F32)
-    a.flags = _conv_flags(mode)
-    buf = ctypes.create_string_buffer(96)
-    return _lib.load().dsm_conv3d_plan(ctypes.byref(a), buf, 96) == _lib.DSM_OK
+    a.flags = flags
+    return a
 
 
 def conv2d_transposed_block(x, packed_weight, cout, out_size, mode=None):
@@ -1426,15 +1426,17 @@ def stage_images_nhwc16(left, right=None):
 # ----------------------------------------------------------------------------
 # the 2-D towers in training: convolution with explicit gradients, batch-statistics BN
 # ----------------------------------------------------------------------------
-# (stride, Cout/32, k, dilation) of the 2-D layers dsm_conv3d_plan accepts in every precision mode (the variant
-# lists of csrc/conv_common.hpp: a split kernel and an fp32-input kernel each); ``blocks2d.fused_ok`` reads this
-# set and tests/test_conv_plans.py holds it against the plan
-_CONV2D_VARIANTS = {(1, 1, 3, 1), (1, 2, 3, 1), (1, 4, 3, 1), (1, 4, 3, 2), (2, 1, 3, 1),
-                    (2, 2, 3, 1), (1, 1, 1, 1), (1, 4, 1, 1), (2, 2, 1, 1)}
-
-
 def conv2d_variant(cout, stride, k, dilation):
-    return cout in (32, 64, 128) and (stride, cout // 32, k, dilation) in _CONV2D_VARIANTS
+    """Is there a kernel for a 1x1 / 3x3 layer of 32 / 64 / 128 outputs in the current precision mode and flags?
+    The plan of a stand-in (16 inputs, a 12 x 40 map: no size decides it); wide and 5x5 layers: see blocks2d."""
+    if cout not in (32, 64, 128) or k not in (1, 3) or stride < 1 or dilation < 1:
+        return False
+    return _conv2d_variant(cout, stride, k, dilation, _mode(None), _conv_flags())
+
+
+@functools.lru_cache(maxsize=None)
+def _conv2d_variant(cout, stride, k, dilation, mode, flags):      # memoised: fused_ok asks per layer and forward
+    return _conv_plan(_conv2d_standin(1, 16, cout, 12, 40, stride, k, dilation, mode, flags))[0] == _lib.DSM_OK
 
 
 def _wgrad2d(x_cl, g_cl, stride, dilation, label="conv2d_wgrad_kernel", mode=None):

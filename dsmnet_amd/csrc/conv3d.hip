@@ -865,29 +865,33 @@ int run_conv(ConvParams p, hipStream_t s, int nsplit = 1) {
   return launch_tiles<conv3d_mfma_kernel<S, NT, TM, CK, KZ, KXY, DIL>>(p, lds, s, 512 / nsplit, nsplit);
 }
 
-// Section 2 of a packed weight buffer (the pre-split bf16 planes), present for the shapes the
-// bf16x3 kernels cover: 3x3x3 with Cout 32/64, 3x3 with Cout 32/64/128; Cin % 16 == 0.
-size_t bf16x3_section_bytes(int Cin, int Cout, int kd, int k) {
-  if (k != 3 || Cin % 16 != 0 || Cout % 32 != 0) return 0;
-  if (Cout > 128) return 0;                            // (3-D, 128 outputs: four workgroup columns of 32, small volumes only)
-  return (size_t)Cin * Cout * kd * 9 * 6;
-}
-// Section 3 (same shapes): a 16-byte header {absolute maximum of the weights, 0, 0, 0} followed by
-// the two fp16 planes of w * 2^ew (conv_split.hpp, PM = 2 | 1).
-// The wide 2-D layers (Cout 256 / 512 / 1024; conv_wide2d.hpp, fp16 modes only) carry section 3 WITHOUT a
-// section 2.
+// The wide 2-D layers (Cout 256 / 512 / 1024; conv_wide2d.hpp, fp16 modes only)
 bool wide2d_layer(int Cin, int Cout, int kd, int k) {
   return kd == 1 && k == 3 && Cin % 16 == 0 && (Cout == 256 || Cout == 512 || Cout == 1024);
 }
-// The 5x5 stride-2 layers (Cout 128 / 256; conv_wide2d.hpp with K = 5) carry section 3 ALONE: no fp32
-// fragments either, the layer has neither an fp32 nor a bf16x3 kernel.
+// The 5x5 stride-2 layers (Cout 128 / 256; conv_wide2d.hpp with K = 5): neither an fp32 nor a bf16x3 kernel
 bool k5_layer(int Cin, int Cout, int kd, int k) {
   return kd == 1 && k == 5 && Cin % 16 == 0 && (Cout == 128 || Cout == 256);
 }
-size_t f16_section_bytes(int Cin, int Cout, int kd, int k) {
-  if (k5_layer(Cin, Cout, kd, k)) return 16 + (size_t)Cin * Cout * 25 * 4;
-  return (bf16x3_section_bytes(Cin, Cout, kd, k) || wide2d_layer(Cin, Cout, kd, k))
-             ? 16 + (size_t)Cin * Cout * kd * 9 * 4 : 0;
+
+// A packed weight buffer: fp32 fragments, pre-split bf16 planes, fp16 section, in this order.  A section the layer
+// has no kernel for has no bytes (5x5: the fp16 section ALONE; wide: no bf16x3).  Packers, size queries, launches.
+struct PackLayout {
+  size_t frag;          // fp32 fragments: every 1x1, 3x3 and 3x3x3 layer
+  size_t bf16x3;        // three bf16 planes: 3x3x3 with Cout 32 / 64 (128: small volumes), 3x3 with Cout 32 / 64 / 128
+  size_t f16;           // 16-byte header {max |w|, 0, 0, 0}, then the two fp16 planes of w * 2^ew (conv_split.hpp, PM = 2 | 1)
+  size_t bytes() const { return frag + bf16x3 + f16; }
+  size_t bf16x3_at() const { return frag; }
+  size_t f16_amax_at() const { return frag + bf16x3; }
+  size_t f16_planes_at() const { return f16_amax_at() + 16; }
+  size_t f16_planes_bytes() const { return f16 - 16; }
+};
+PackLayout pack_layout(int Cin, int Cout, int kd, int k) {
+  const size_t n = (size_t)Cin * Cout * kd * k * k;
+  PackLayout L{k == 5 ? 0 : n * 4, 0, 0};
+  if (k == 3 && Cin % 16 == 0 && Cout % 32 == 0 && Cout <= 128) L.bf16x3 = n * 6;
+  if (L.bf16x3 || wide2d_layer(Cin, Cout, kd, k) || k5_layer(Cin, Cout, kd, k)) L.f16 = 16 + n * 4;
+  return L;
 }
 
 // Conv3d(k3, s1) to 32 channels from Cin % 32 == 0 runs on the z-sliding kernel (conv_zs.hpp):
@@ -896,33 +900,36 @@ bool zs_layer(int Cin, int Cout, int kd, int k, int transposed) {
   return kd == 3 && k == 3 && !transposed && Cout == 32 && Cin % 32 == 0;
 }
 
-// the split sections behind the fp32 fragments of a packed buffer (`frag` = its first byte)
-int pack_split_sections(const float* w, char* frag, int Cin_src, int Cin, int Cout, int kd, int k,
-                        int transposed, hipStream_t s) {
+// every section of a packed buffer (`packed` = its first byte): both pack entry points
+int pack_sections(const float* w, char* packed, int Cin_src, int Cin, int Cout, int kd, int k,
+                  int transposed, hipStream_t s) {
   const int ntaps = kd * k * k;
   const long n = (long)Cin * Cout * ntaps;
-  if (!f16_section_bytes(Cin, Cout, kd, k)) return DSM_OK;
-  const bool has2 = bf16x3_section_bytes(Cin, Cout, kd, k) != 0;
-  char* sec2 = frag + n * 4;
-  char* sec3 = sec2 + bf16x3_section_bytes(Cin, Cout, kd, k);
+  const PackLayout L = pack_layout(Cin, Cout, kd, k);
+  if (L.frag)
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, w, (float*)packed, Cin, Cout,
+                       transposed, ntaps, Cin_src);
+  if (!L.f16) return DSM_OK;
+  unsigned short* const bf = (unsigned short*)(packed + L.bf16x3_at());
+  float* const amax = (float*)(packed + L.f16_amax_at());
+  unsigned short* const planes = (unsigned short*)(packed + L.f16_planes_at());
   const bool zs = zs_layer(Cin, Cout, kd, k, transposed) && Cin_src == Cin;
-  if (!has2) {}
-  else if (zs)
+  if (L.bf16x3 && zs)
     hipLaunchKernelGGL(pack_weights_zs_kernel<3>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, w,
-                       (unsigned short*)sec2, (const float*)nullptr, Cin);
-  else
-  hipLaunchKernelGGL(pack_weights_split_kernel<3>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, w,
-                     (unsigned short*)sec2, (const float*)nullptr, Cin, Cout, transposed, ntaps, Cin_src);
-  if (hipMemsetAsync(sec3, 0, 16, s) != hipSuccess) return DSM_ERR_LAUNCH;
+                       bf, (const float*)nullptr, Cin);
+  else if (L.bf16x3)
+    hipLaunchKernelGGL(pack_weights_split_kernel<3>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, w,
+                       bf, (const float*)nullptr, Cin, Cout, transposed, ntaps, Cin_src);
+  if (hipMemsetAsync(amax, 0, 16, s) != hipSuccess) return DSM_ERR_LAUNCH;
   const long nsrc = (long)Cin_src * Cout * ntaps;
   hipLaunchKernelGGL(absmax_kernel, dim3(dsm_cdiv(dsm_cdiv(nsrc, 4), 256) < 64 ? dsm_cdiv(dsm_cdiv(nsrc, 4), 256) : 64),
-                     dim3(256), 0, s, w, nsrc, (float*)sec3);
+                     dim3(256), 0, s, w, nsrc, amax);
   if (zs)
     hipLaunchKernelGGL(pack_weights_zs_kernel<2>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, w,
-                       (unsigned short*)(sec3 + 16), (const float*)sec3, Cin);
+                       planes, (const float*)amax, Cin);
   else
-  hipLaunchKernelGGL(pack_weights_split_kernel<2>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, w,
-                     (unsigned short*)(sec3 + 16), (const float*)sec3, Cin, Cout, transposed, ntaps, Cin_src);
+    hipLaunchKernelGGL(pack_weights_split_kernel<2>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, s, w,
+                       planes, (const float*)amax, Cin, Cout, transposed, ntaps, Cin_src);
   return DSM_OK;
 }
 
@@ -948,8 +955,7 @@ int run_deconv(ConvParams p, hipStream_t s) {
 extern "C" size_t dsm_conv3d_packed_weight_bytes(int Cin, int Cout, int transposed) {
   (void)transposed;
   if (Cin <= 0 || Cout <= 0) return 0;
-  return (size_t)Cin * Cout * 27 * sizeof(float) + bf16x3_section_bytes(Cin, Cout, 3, 3) +
-         f16_section_bytes(Cin, Cout, 3, 3);
+  return pack_layout(Cin, Cout, 3, 3).bytes();
 }
 
 extern "C" int dsm_conv3d_pack_weights(const void* w_torch, void* w_packed, int Cin, int Cout,
@@ -957,13 +963,9 @@ extern "C" int dsm_conv3d_pack_weights(const void* w_torch, void* w_packed, int 
   DSM_REQUIRE(w_torch && w_packed && w_torch != w_packed, DSM_ERR_ARG);
   DSM_REQUIRE(Cin > 0 && Cout > 0, DSM_ERR_ARG);
   DSM_REQUIRE(Cin % 8 == 0 && (Cout == 1 || Cout % 32 == 0), DSM_ERR_UNSUPPORTED);
-  const long n = (long)Cin * Cout * 27;
   dsm_clear_stale_error();
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(dsm_cdiv(n, 256)), dim3(256), 0,
-                     (hipStream_t)stream, (const float*)w_torch, (float*)w_packed, Cin, Cout,
-                     transposed, 27, Cin);
-  const int rc = pack_split_sections((const float*)w_torch, (char*)w_packed, Cin, Cin, Cout, 3, 3,
-                                     transposed, (hipStream_t)stream);
+  const int rc = pack_sections((const float*)w_torch, (char*)w_packed, Cin, Cin, Cout, 3, 3, transposed,
+                               (hipStream_t)stream);
   return rc != DSM_OK ? rc : dsm_launch_status();
 }
 
@@ -973,25 +975,9 @@ extern "C" int dsm_conv_pack_weights(const void* w_torch, void* w_packed, int Ci
   DSM_REQUIRE(Cin_src > 0 && Cin >= Cin_src && Cout > 0, DSM_ERR_ARG);
   DSM_REQUIRE(((kd == 1 || kd == 3) && (k == 1 || k == 3)) || k5_layer(Cin, Cout, kd, k), DSM_ERR_UNSUPPORTED);
   DSM_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0, DSM_ERR_UNSUPPORTED);
-  const int ntaps = kd * k * k;
-  const long n = (long)Cin * Cout * ntaps;
   dsm_clear_stale_error();
-  if (k == 5) {                                          // the fp16 section alone: header, two planes
-    char* const sec3 = (char*)w_packed;
-    if (hipMemsetAsync(sec3, 0, 16, (hipStream_t)stream) != hipSuccess) return DSM_ERR_LAUNCH;
-    const long nsrc = (long)Cin_src * Cout * ntaps, nb = dsm_cdiv(dsm_cdiv(nsrc, 4), 256);
-    hipLaunchKernelGGL(absmax_kernel, dim3(nb < 64 ? nb : 64), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)w_torch, nsrc, (float*)sec3);
-    hipLaunchKernelGGL(pack_weights_split_kernel<2>, dim3(dsm_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)w_torch, (unsigned short*)(sec3 + 16), (const float*)sec3, Cin, Cout, 0, ntaps,
-                       Cin_src);
-    return dsm_launch_status();
-  }
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(dsm_cdiv(n, 256)), dim3(256), 0,
-                     (hipStream_t)stream, (const float*)w_torch, (float*)w_packed, Cin, Cout, 0,
-                     ntaps, Cin_src);
-  const int rc = pack_split_sections((const float*)w_torch, (char*)w_packed, Cin_src, Cin, Cout, kd, k,
-                                     0, (hipStream_t)stream);
+  const int rc = pack_sections((const float*)w_torch, (char*)w_packed, Cin_src, Cin, Cout, kd, k, 0,
+                               (hipStream_t)stream);
   return rc != DSM_OK ? rc : dsm_launch_status();
 }
 
@@ -1007,10 +993,8 @@ extern "C" int dsm_absmax(const void* x, size_t n, float* amax, dsm_stream_t str
 
 extern "C" size_t dsm_conv_packed_weight_bytes(int Cin, int Cout, int kd, int k) {
   if (Cin <= 0 || Cout <= 0) return 0;
-  if (k5_layer(Cin, Cout, kd, k)) return f16_section_bytes(Cin, Cout, kd, k);
-  if (!((kd == 1 || kd == 3) && (k == 1 || k == 3))) return 0;
-  return (size_t)Cin * Cout * kd * k * k * sizeof(float) + bf16x3_section_bytes(Cin, Cout, kd, k) +
-         f16_section_bytes(Cin, Cout, kd, k);
+  if (!(((kd == 1 || kd == 3) && (k == 1 || k == 3)) || k5_layer(Cin, Cout, kd, k))) return 0;
+  return pack_layout(Cin, Cout, kd, k).bytes();
 }
 
 namespace {
@@ -1018,11 +1002,11 @@ namespace {
 // Work decomposition of a wide 2-D layer (conv_wide2d.hpp), a pure function of the arguments: M-block,
 // N-column width (64, or 32 where 64-wide columns cannot give every CU a workgroup), K-ranges.
 // flags bits 8..13 force the number of K-ranges (clamped to the 16-channel chunks there are).
-// The 5x5 layers (kind 10) share it: their window is in a->k.
+// The 5x5 layers (KIND_K5) share it: their window is in a->k.
 bool wide2d_units(const dsm_conv3d_args* a, WideParams* w) {
   w->K = a->k == 5 ? 5 : 3;
   w->B = a->B; w->Cin = a->Cin; w->Cout = a->Cout; w->Hi = a->Hi; w->Wi = a->Wi; w->Ho = a->Ho; w->Wo = a->Wo;
-  w->S = a->transposed ? 1 : a->stride;              // transposed (kind 9): the stride-1 geometry over Ho x Wo
+  w->S = a->transposed ? 1 : a->stride;              // transposed (KIND_WIDE_TR): the stride-1 geometry over Ho x Wo
   if (!dsmk::wide2d_geometry(*w)) return false;
   // at most eight chunks (216 MFMA roundings of the fp32 accumulator) per range: the tower layers hold the
   // f16x2 error band with chains of 540; a 64-chunk chain (conv6b unsplit, 1,728) would leave it
@@ -1043,7 +1027,46 @@ bool wide2d_units(const dsm_conv3d_args* a, WideParams* w) {
   return true;
 }
 
-int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
+// The shared tail of the three wide plans (KIND_WIDE, KIND_WIDE_TR, KIND_K5), behind each kind's own preconditions:
+// fp16 modes only; 32-bit offsets with the out-of-range marker at 2^31; the work units.
+int wide_plan(const dsm_conv3d_args* a, Kind kind, Plan* pl) {
+  DSM_REQUIRE(a->precision != DSM_PREC_F32 && bf16x3_enabled(a), DSM_ERR_UNSUPPORTED);
+  DSM_REQUIRE(4ul * a->B * a->Hi * a->Wi * a->Cin < 0x80000000ul &&
+              (unsigned long)a->B * a->Ho * a->Wo * a->Cout < 0x7fffffffUL, DSM_ERR_UNSUPPORTED);
+  WideParams w;
+  DSM_REQUIRE(wide2d_units(a, &w), DSM_ERR_UNSUPPORTED);
+  *pl = Plan{kind, a->stride, w.nwn, w.nunits, 16, 1, w.K, 1};     // (TM: the work units)
+  pl->nsplit = w.ksplit;
+  return DSM_OK;
+}
+
+// The fp32-input MFMA kernels (KIND_CONV): every layer that no split kernel takes.
+int fp32_plan(const dsm_conv3d_args* a, int kd, int k, int dil, Plan* pl) {
+  const int NT = a->Cout / 32;
+  // Tile height: 8 rows (TM = 2) when that still gives every CU two workgroups of work,
+  // else 4 rows.  Stride 2 stages 8 channels per chunk so that two workgroups fit a CU.
+  const bool big = (long)a->B * a->Do * dsm_cdiv(a->Ho, 8) * dsm_cdiv(a->Wo, 32) >= 1024;
+  if (kd == 1) {                                   // 2-D towers: one staged slice, 16-channel chunks
+    const int TM = (big && NT == 1 && a->stride == 1 && k == 3 && dil == 1) ? 2 : 1;
+    *pl = Plan{KIND_CONV, a->stride, NT, TM, 16, 1, k, dil};
+    return DSM_OK;
+  }
+  if (a->stride == 1) {
+    const int force_tm = forced_tm(a) <= 2 ? forced_tm(a) : 0;     // tile-height A/B runs
+    const int TM = force_tm ? force_tm : ((big && NT <= 2) ? 2 : 1);
+    *pl = Plan{KIND_CONV, 1, NT, TM, (NT == 2 && TM == 2) ? 8 : 16, 3, 3, 1};   // <1,2,2,16> would spill
+  } else {
+    *pl = Plan{KIND_CONV, 2, NT, 1, 8, 3, 3, 1};
+  }
+  // N-split: a layer with few tiles and several N-tiles runs the NT = 1 variant with one
+  // workgroup column per N-tile (4x the workgroups, each a quarter as long)
+  const long tiles4 = (long)a->B * a->Do * dsm_cdiv(a->Ho, 4) * dsm_cdiv(a->Wo, 32);
+  if (NT >= 2 && tiles4 <= 64 && pl->TM == 1) { pl->nsplit = NT; pl->NT = 1; }
+  return DSM_OK;
+}
+
+// Which kernel family and variant the arguments ask for.  Looks at no x_amax and at no variant list.
+int select_kernel(const dsm_conv3d_args* a, Plan* pl) {
   DSM_REQUIRE(a && a->x && a->w_packed && a->y, DSM_ERR_ARG);
   DSM_REQUIRE(a->B > 0 && a->Cin > 0 && a->Cout > 0, DSM_ERR_ARG);
   DSM_REQUIRE(a->Di > 0 && a->Hi > 0 && a->Wi > 0 && a->Do > 0 && a->Ho > 0 && a->Wo > 0,
@@ -1058,38 +1081,24 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
   const int kd = a->kd ? a->kd : 3, k = a->k ? a->k : 3, dil = a->dil ? a->dil : 1;
   if (k == 5) {
     // the 5x5 stride-2 layers (DispNet conv2 / conv3a; conv2 of DispNetC / iResNet): conv_wide2d.hpp with
-    // K = 5, fp16 modes only, no skip input, the natural output size; 32-bit offsets with the out-of-range
-    // marker at 2^31.  (This check sits before the generic Cout 32 / 64 / 128 path: Cout = 128 is both.)
+    // K = 5, no skip input, the natural output size.  (This check sits before the generic Cout 32 / 64 / 128
+    // path: Cout = 128 is both.)
     DSM_REQUIRE(k5_layer(a->Cin, a->Cout, kd, k) && dil == 1 && a->stride == 2 && !a->transposed &&
                 !a->vol_virtual && !a->residual && a->Di == 1 && a->Do == 1 &&
                 a->Ho == (a->Hi - 1) / 2 + 1 && a->Wo == (a->Wi - 1) / 2 + 1, DSM_ERR_UNSUPPORTED);
-    DSM_REQUIRE(a->precision != DSM_PREC_F32 && bf16x3_enabled(a), DSM_ERR_UNSUPPORTED);
-    DSM_REQUIRE(4ul * a->B * a->Hi * a->Wi * a->Cin < 0x80000000ul &&
-                (unsigned long)a->B * a->Ho * a->Wo * a->Cout < 0x7fffffffUL, DSM_ERR_UNSUPPORTED);
-    WideParams w;
-    DSM_REQUIRE(wide2d_units(a, &w), DSM_ERR_UNSUPPORTED);
-    *pl = Plan{10, 2, w.nwn, w.nunits, 16, 1, 5, 1};     // (TM: the work units)
-    pl->nsplit = w.ksplit;
-    return DSM_OK;
+    return wide_plan(a, KIND_K5, pl);
   }
   DSM_REQUIRE((kd == 1 || kd == 3) && (k == 1 || k == 3) && (dil == 1 || dil == 2),
               DSM_ERR_UNSUPPORTED);
   if (kd == 1 && a->transposed) {
     // the one transposed 2-D plan: backward-data of the stride-2 wide layers (conv_wide2d.hpp, TR).  y is the
     // stride-1 convolution of the zero-interleaved x over Ho x Wo, 2 Hi - 1 <= Ho <= 2 Hi (the extent of the
-    // tensor whose gradient this is); fp16 modes only, no skip input
+    // tensor whose gradient this is); no skip input
     DSM_REQUIRE(k == 3 && dil == 1 && a->stride == 2 && a->Di == 1 && a->Do == 1 &&
                 wide2d_layer(a->Cin, a->Cout, kd, k) && !a->vol_virtual && !a->residual, DSM_ERR_UNSUPPORTED);
     DSM_REQUIRE(a->Ho <= 2 * a->Hi && a->Wo <= 2 * a->Wi &&
                 a->Ho >= 2 * a->Hi - 1 && a->Wo >= 2 * a->Wi - 1, DSM_ERR_UNSUPPORTED);
-    DSM_REQUIRE(a->precision != DSM_PREC_F32 && bf16x3_enabled(a), DSM_ERR_UNSUPPORTED);
-    DSM_REQUIRE(4ul * a->B * a->Hi * a->Wi * a->Cin < 0x80000000ul &&
-                (unsigned long)a->B * a->Ho * a->Wo * a->Cout < 0x7fffffffUL, DSM_ERR_UNSUPPORTED);
-    WideParams w;
-    DSM_REQUIRE(wide2d_units(a, &w), DSM_ERR_UNSUPPORTED);
-    *pl = Plan{9, 2, w.nwn, w.nunits, 16, 1, 3, 1};
-    pl->nsplit = w.ksplit;
-    return DSM_OK;
+    return wide_plan(a, KIND_WIDE_TR, pl);
   }
   DSM_REQUIRE(kd == 3 ? (k == 3 && dil == 1) : (!a->transposed && a->Di == 1 && a->Cout != 1),
               DSM_ERR_UNSUPPORTED);
@@ -1103,40 +1112,30 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
   if (a->Cout == 1) {
     if (a->transposed) {
       DSM_REQUIRE(a->Cin == 32, DSM_ERR_UNSUPPORTED);      // GCNet l37 (staged as whole voxels)
-      *pl = Plan{3, 2, 0, 0, 0, 3, 3, 1};
+      *pl = Plan{KIND_DECONV_COUT1, 2, 0, 0, 0, 3, 3, 1};
     } else {
       DSM_REQUIRE(a->stride == 1, DSM_ERR_UNSUPPORTED);
       const bool zslide = !(a->flags & DSM_CONV_COUT1_CHUNKED);      // A/B runs: the chunked kernel
-      *pl = Plan{(a->Cin == 32 && zslide) ? 4 : 2, 1, 0, 0, 8, 3, 3, 1};
+      *pl = Plan{(a->Cin == 32 && zslide) ? KIND_COUT1_ZS : KIND_COUT1, 1, 0, 0, 8, 3, 3, 1};
     }
     return DSM_OK;
   }
   if (a->Cout == 256 || a->Cout == 512 || a->Cout == 1024) {
-    // the wide 2-D layers (DispNetC / iResNet encoder): conv_wide2d.hpp, fp16 modes only, no skip input,
-    // the natural output size; 32-bit offsets with the out-of-range marker at 2^31
+    // the wide 2-D layers (DispNetC / iResNet encoder): conv_wide2d.hpp, no skip input, the natural output size
     DSM_REQUIRE(wide2d_layer(a->Cin, a->Cout, kd, k) && dil == 1 && !a->transposed && !a->vol_virtual &&
                 !a->residual && a->Ho == nH && a->Wo == nW, DSM_ERR_UNSUPPORTED);
-    DSM_REQUIRE(a->precision != DSM_PREC_F32 && bf16x3_enabled(a), DSM_ERR_UNSUPPORTED);
-    DSM_REQUIRE(4ul * a->B * a->Hi * a->Wi * a->Cin < 0x80000000ul &&
-                (unsigned long)a->B * a->Ho * a->Wo * a->Cout < 0x7fffffffUL, DSM_ERR_UNSUPPORTED);
-    WideParams w;
-    DSM_REQUIRE(wide2d_units(a, &w), DSM_ERR_UNSUPPORTED);
-    *pl = Plan{8, a->stride, w.nwn, w.nunits, 16, 1, 3, 1};      // (TM: the work units)
-    pl->nsplit = w.ksplit;
-    return DSM_OK;
+    return wide_plan(a, KIND_WIDE, pl);
   }
   DSM_REQUIRE(a->Cout == 32 || a->Cout == 64 || a->Cout == 128, DSM_ERR_UNSUPPORTED);
   const int NT = a->Cout / 32;
-  // Tile height: 8 rows (TM = 2) when that still gives every CU two workgroups of work,
-  // else 4 rows.  Stride 2 stages 8 channels per chunk so that two workgroups fit a CU.
   if (a->transposed && NT <= 2 && a->Cin % 32 == 0 && bf16x3_enabled(a) &&
       4l * a->B * a->Di * a->Hi * a->Wi * a->Cin < 0x80000000l) {
-    *pl = Plan{6, 2, NT, 1, 32, 3, 3, 1};
+    *pl = Plan{KIND_DECONV_SPLIT, 2, NT, 1, 32, 3, 3, 1};
     return DSM_OK;
   }
   if (a->transposed) {
     DSM_REQUIRE(NT <= 2, DSM_ERR_UNSUPPORTED);   // 4 classes x NT accumulators must fit 256 VGPRs
-    *pl = Plan{1, 2, NT, 1, 16, 3, 3, 1};   // (32-channel chunks measured slower: 306 vs 283 us)
+    *pl = Plan{KIND_DECONV, 2, NT, 1, 16, 3, 3, 1};   // (32-channel chunks measured slower: 306 vs 283 us)
     return DSM_OK;
   }
   // 32-bit offsets per input plane, the out-of-range marker (2^31) past its descriptor: a virtual volume's
@@ -1145,12 +1144,11 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
       (a->vol_virtual ? ((unsigned long)a->Hi * a->Wi + a->Di - 1) * a->Cin * 2ul
                       : (unsigned long)a->Hi * a->Wi * a->Cin * 4ul) < 0x7fffffffUL) {
     if (a->vol_virtual) DSM_REQUIRE(a->Cin % 64 == 0, DSM_ERR_UNSUPPORTED);   // [left | right], 32-channel groups each
-    *pl = Plan{7, 1, 1, 2, 32, 3, 3, 1};
+    *pl = Plan{KIND_ZS, 1, 1, 2, 32, 3, 3, 1};
     return DSM_OK;
   }
   DSM_REQUIRE(!a->vol_virtual, DSM_ERR_UNSUPPORTED);   // only the z-sliding kernel stages a virtual volume
-  const bool big = (long)a->B * a->Do * dsm_cdiv(a->Ho, 8) * dsm_cdiv(a->Wo, 32) >= 1024;
-  if (a->stride == 1 && k == 3 && bf16x3_enabled(a) && bf16x3_section_bytes(a->Cin, a->Cout, kd, k) &&
+  if (a->stride == 1 && k == 3 && bf16x3_enabled(a) && pack_layout(a->Cin, a->Cout, kd, k).bf16x3 &&
       4l * a->B * a->Di * a->Hi * a->Wi * a->Cin < 0x80000000l) {       // OOBV must lie past the tensor
     // fp32 on the bf16 pipe.  16-row tiles (TM = 4) when they still give every CU a workgroup,
     // else 8-row tiles; 64 and 128 output channels always take 8-row tiles (accumulators).
@@ -1166,7 +1164,7 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
     const long tiles8 = (long)a->B * a->Do * dsm_cdiv(a->Ho, 8) * dsm_cdiv(a->Wo, 32);
     if (NT == 2 && dil == 1 && tiles8 < 192) TM = 1;
     if (force_tm == 2 || (force_tm == 4 && NT == 1 && dil == 1) || (force_tm == 1 && NT == 2 && dil == 1)) TM = force_tm;
-    *pl = Plan{5, 1, NT, TM, 16, kd, 3, dil};
+    *pl = Plan{KIND_SPLIT, 1, NT, TM, 16, kd, 3, dil};
     // N-split (2-D layers, fp32 input): at most one round of 8-row tiles -- every workgroup's prologue
     // and epilogue exposed -- becomes two workgroup columns of half the output blocks, two per CU
     if (kd == 1 && TM == 2 && dil == 1 && (NT == 2 || NT == 4) && tiles8 <= 256 &&
@@ -1183,8 +1181,8 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
     // 4-row tiles; larger volumes of that width stay on the fp32-input kernel (no NT = 4 3-D variant)
     if (kd == 3 && NT == 4) {
       const long t4 = (long)a->B * a->Do * dsm_cdiv(a->Ho, 4) * dsm_cdiv(a->Wo, 32);
-      if (t4 <= 128 && dil == 1) { *pl = Plan{5, 1, 1, 1, 16, 3, 3, 1}; pl->nsplit = 4; return DSM_OK; }
-      goto fp32_kernels;
+      if (t4 <= 128 && dil == 1) { *pl = Plan{KIND_SPLIT, 1, 1, 1, 16, 3, 3, 1}; pl->nsplit = 4; return DSM_OK; }
+      return fp32_plan(a, kd, k, dil, pl);
     }
     if (kd == 3 && TM == 1 && NT == 2 && !(a->flags & DSM_CONV_NO_NSPLIT) &&
         (long)a->B * a->Do * dsm_cdiv(a->Ho, 4) * dsm_cdiv(a->Wo, 32) <= 256) {
@@ -1194,57 +1192,168 @@ int select_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
   }
   if (a->stride == 2 && kd == 3 && NT == 2 && bf16x3_enabled(a) &&
       4l * a->B * a->Di * a->Hi * a->Wi * a->Cin < 0x80000000l) {
-    *pl = Plan{5, 2, 2, 1, 16, 3, 3, 1};           // stride 2 on the bf16 pipe: 4-row tiles, Cout = 64
+    *pl = Plan{KIND_SPLIT, 2, 2, 1, 16, 3, 3, 1};  // stride 2 on the bf16 pipe: 4-row tiles, Cout = 64
     return DSM_OK;
   }
-fp32_kernels:
-  if (kd == 1) {                                   // 2-D towers: one staged slice, 16-channel chunks
-    const int TM = (big && NT == 1 && a->stride == 1 && k == 3 && dil == 1) ? 2 : 1;
-    *pl = Plan{0, a->stride, NT, TM, 16, 1, k, dil};
-    return DSM_OK;
-  }
-  if (a->stride == 1) {
-    const int force_tm = forced_tm(a) <= 2 ? forced_tm(a) : 0;     // tile-height A/B runs
-    const int TM = force_tm ? force_tm : ((big && NT <= 2) ? 2 : 1);
-    *pl = Plan{0, 1, NT, TM, (NT == 2 && TM == 2) ? 8 : 16, 3, 3, 1};   // <1,2,2,16> would spill
-  } else {
-    *pl = Plan{0, 2, NT, 1, 8, 3, 3, 1};
-  }
-  // N-split: a layer with few tiles and several N-tiles runs the NT = 1 variant with one
-  // workgroup column per N-tile (4x the workgroups, each a quarter as long)
-  const long tiles4 = (long)a->B * a->Do * dsm_cdiv(a->Ho, 4) * dsm_cdiv(a->Wo, 32);
-  if (NT >= 2 && tiles4 <= 64 && pl->TM == 1) { pl->nsplit = NT; pl->NT = 1; }
-  return DSM_OK;
+  return fp32_plan(a, kd, k, dil, pl);
 }
-// The selection above, refused where it names a variant that is not compiled (conv_common.hpp): the plan
-// query, the workspace query and the launch all start here, so they return the same code.
-int make_plan_f32(const dsm_conv3d_args* a, Plan* pl) {
-  const int rc = select_plan_f32(a, pl);
+// The selection above, refused where it names a variant that is not compiled (conv_common.hpp), then its precision
+// mode: plan query, workspace query (`need_amax` false: it answers without an x_amax) and launch start here.
+int make_plan(const dsm_conv3d_args* a, Plan* pl, bool need_amax = true) {
+  const int rc = select_kernel(a, pl);
   if (rc != DSM_OK) return rc;
-  if (pl->kind != 7 && pl->kind != 8 && pl->kind != 9 && pl->kind != 10) { // 32-bit buffer offsets (kinds 7 .. 10 bound theirs above)
+  if (!kind_bounds_own_extents(pl->kind)) {              // 32-bit buffer offsets
     const int kd = a->kd ? a->kd : 3, k = a->k ? a->k : 3;
     DSM_REQUIRE(4ul * a->B * a->Di * a->Hi * a->Wi * a->Cin < (1ul << 32) &&
                 4ul * a->Cin * a->Cout * kd * k * k < (1ul << 32), DSM_ERR_UNSUPPORTED);
   }
-  return plan_compiled(*pl) ? DSM_OK : DSM_ERR_UNSUPPORTED;
-}
-// precision: the split kernels (kinds 5, 6) also exist on fp16 terms (conv_split.hpp); every other
-// kernel computes in fp32 whatever `precision` says
-int make_plan(const dsm_conv3d_args* a, Plan* pl) {
-  const int rc = make_plan_f32(a, pl);
-  if (rc != DSM_OK) return rc;
+  if (!plan_compiled(*pl)) return DSM_ERR_UNSUPPORTED;
   pl->pm = 3;
-  if ((pl->kind == 5 || pl->kind == 6 || pl->kind == 7 || pl->kind == 8 || pl->kind == 9 || pl->kind == 10) && a->precision != DSM_PREC_F32) {
-    DSM_REQUIRE(a->x_amax != nullptr, DSM_ERR_ARG);      // the input's absolute maximum (device scalar)
+  if (kind_scales_operands(pl->kind) && a->precision != DSM_PREC_F32) {
+    DSM_REQUIRE(a->x_amax != nullptr || !need_amax, DSM_ERR_ARG);      // the input's absolute maximum (device scalar)
     pl->pm = a->precision == DSM_PREC_F16X2 ? 2 : 1;
   }
   if (pl->pm == 3) pl->once = 0;                         // the single-tile form exists in the fp16 modes only
   // transposed layers of 64+ inputs in the fp16 modes: the z-sliding kernel (deconv_zs.hpp; two or more
   // 32-channel groups: one exchange buffer; 32-bit offsets within an input plane)
-  if (pl->kind == 6 && pl->pm != 3 && DSM_DECONV_ZS && a->Cin % 64 == 0 &&
+  if (pl->kind == KIND_DECONV_SPLIT && pl->pm != 3 && DSM_DECONV_ZS && a->Cin % 64 == 0 &&
       4l * a->Hi * a->Wi * a->Cin < 0x7fffffffl)
     pl->zs = 1;
   return DSM_OK;
+}
+const char* prec_name(int pm) { return pm == 3 ? "bf16x3" : (pm == 2 ? "f16x2" : "f16"); }
+// the K-split partial sums of a wide plan: [ksplit][B*Ho*Wo][Cout] floats
+size_t wide_workspace_bytes(const dsm_conv3d_args* a, const Plan& pl) {
+  return pl.nsplit <= 1 ? 0 : (size_t)pl.nsplit * a->B * a->Ho * a->Wo * a->Cout * sizeof(float);
+}
+inline int forced_blocks(const dsm_conv3d_args* a) { return (a->flags >> DSM_CONV_BLOCKS_SHIFT) & 0xffff; }
+
+// The launches: each fills the parameter struct its kernels read.
+int launch_wide(const dsm_conv3d_args* a, const Plan& pl, hipStream_t s) {
+  const size_t need = wide_workspace_bytes(a, pl);
+  DSM_REQUIRE(need == 0 || (a->workspace && a->workspace_bytes >= need), DSM_ERR_ARG);
+  DSM_REQUIRE(need == 0 || dsm_aligned16(a->workspace), DSM_ERR_ALIGN);
+  WideParams w; wide2d_units(a, &w);
+  // (a 5x5 layer's packed buffer IS its fp16 section; a 3x3 layer's section lies behind the fp32 fragments)
+  const PackLayout L = pack_layout(a->Cin, a->Cout, 1, w.K);
+  const char* const wp = (const char*)a->w_packed;
+  w.x = (const float*)a->x; w.w = (const unsigned char*)(wp + L.f16_planes_at()); w.w_amax = (const float*)(wp + L.f16_amax_at());
+  w.scale = a->scale; w.shift = a->shift; w.y = (float*)a->y; w.ws = (float*)a->workspace;
+  w.x_amax = a->x_amax; w.y_amax = a->y_amax; w.relu = a->relu ? 1 : 0;
+  w.xbytes = (unsigned)(4ul * a->B * a->Hi * a->Wi * a->Cin);
+  w.wbytes = (unsigned)L.f16_planes_bytes();
+  int grid = forced_blocks(a);                                  // forced grid: the units are walked in a loop
+  if (grid <= 0 || grid > w.nunits) grid = w.nunits;
+  dsm_clear_stale_error();
+  return dsmk::run_wide2d_f16(pl.pm, w, grid, pl.kind == KIND_WIDE_TR, s);
+}
+
+int launch_zs(const dsm_conv3d_args* a, const Plan& pl, hipStream_t s) {
+  // the layer is Conv3d(Cin -> 32, k3): its bf16x3 section is Cin * 32 * 27 * 6 bytes, its fp16 planes * 4
+  // (Cin % 32 == 0, so pack_layout gives it both sections)
+  const PackLayout L = pack_layout(a->Cin, 32, 3, 3);
+  const char* const wp = (const char*)a->w_packed;
+  ZsParams z;
+  z.x = (const float*)a->x; z.scale = a->scale; z.shift = a->shift; z.res = (const float*)a->residual;
+  z.y = (float*)a->y; z.x_amax = a->x_amax; z.y_amax = a->y_amax;
+  z.w_amax = pl.pm == 3 ? nullptr : (const float*)(wp + L.f16_amax_at());
+  z.w = (const unsigned char*)(wp + (pl.pm == 3 ? L.bf16x3_at() : L.f16_planes_at()));
+  z.wbytes = (unsigned)(pl.pm == 3 ? L.bf16x3 : L.f16_planes_bytes());
+  z.B = a->B; z.Cin = a->Cin;
+  z.Di = a->Di; z.Hi = a->Hi; z.Wi = a->Wi; z.Do = a->Do; z.Ho = a->Ho; z.Wo = a->Wo;
+  z.Dr = a->Dr; z.Hr = a->Hr; z.Wr = a->Wr; z.relu = a->relu;
+  z.vol = a->vol_virtual ? 1 : 0; z.vol_mask_left = a->vol_mask_left ? 1 : 0;
+  dsm_clear_stale_error();
+  if (pl.pm == 3) return launch_conv_zs<3>(z, forced_blocks(a), s);
+  return dsmk::run_zs_f16(pl.pm, z, forced_blocks(a), s);
+}
+
+// the tile kernels' struct (every kind but the wide and the z-sliding one); p.w: the fp32 fragments.  The launch
+// follows: a stale error of an earlier call is dropped here, as the other two launches do before theirs.
+ConvParams conv_params(const dsm_conv3d_args* a) {
+  ConvParams p;
+  p.x = (const float*)a->x; p.w = (const float*)a->w_packed; p.scale = a->scale;
+  p.x_amax = a->x_amax; p.w_amax = nullptr; p.y_amax = a->y_amax;
+  p.shift = a->shift; p.res = (const float*)a->residual; p.y = (float*)a->y;
+  p.force_blocks = forced_blocks(a);
+  p.single_kind = (a->flags & DSM_CONV_NO_ONCE) ? 1 : 0;
+  p.B = a->B; p.Cin = a->Cin; p.Cout = a->Cout;
+  p.Di = a->Di; p.Hi = a->Hi; p.Wi = a->Wi; p.Do = a->Do; p.Ho = a->Ho; p.Wo = a->Wo;
+  p.Dr = a->Dr; p.Hr = a->Hr; p.Wr = a->Wr; p.relu = a->relu;
+  p.ntx = p.nty = p.ntiles = 0;
+  // 32-bit buffer offsets: make_plan has refused extents of 4 GiB and more
+  p.xbytes = (unsigned)(4ul * a->B * a->Di * a->Hi * a->Wi * a->Cin);
+  p.wbytes = (unsigned)(4ul * a->Cin * a->Cout * (a->kd ? a->kd : 3) * (a->k ? a->k : 3) * (a->k ? a->k : 3));
+  dsm_clear_stale_error();
+  return p;
+}
+
+int launch_split(const dsm_conv3d_args* a, const Plan& pl, hipStream_t s) {
+  ConvParams p = conv_params(a);
+  const PackLayout L = pack_layout(a->Cin, a->Cout, pl.kind == KIND_DECONV_SPLIT ? 3 : pl.KZ, 3);
+  const char* const wp = (const char*)a->w_packed;
+  if (pl.pm == 3) {
+    p.w = (const float*)(wp + L.bf16x3_at());
+    p.wbytes = (unsigned)L.bf16x3;
+    return dispatch_split<3>(pl, p, s);
+  }
+  p.w_amax = (const float*)(wp + L.f16_amax_at());
+  p.w = (const float*)(wp + L.f16_planes_at());
+  p.wbytes = (unsigned)L.f16_planes_bytes();
+  return dsmk::run_split_f16(pl, p, s);
+}
+
+int launch_deconv_cout1(ConvParams p, hipStream_t s) {
+  p.ntx = dsm_cdiv(p.Wi, 32); p.nty = dsm_cdiv(p.Hi, 4);
+  const long nt = (long)p.B * p.Di * p.nty * p.ntx;
+  DSM_REQUIRE(nt < (1L << 31), DSM_ERR_UNSUPPORTED);
+  const size_t lds = (size_t)(2 * 5 * 33 * 8 + 27 * 8) * 16;     // 45.7 KB
+  hipLaunchKernelGGL(deconv3d_cout1_kernel, dim3((unsigned)nt), dim3(NTHREADS), lds, s, p);
+  return dsm_launch_status();
+}
+
+int launch_cout1_zs(ConvParams p, hipStream_t s) {
+  p.ntx = dsm_cdiv(p.Wo, 32); p.nty = dsm_cdiv(p.Ho, 8);
+  // z-segment: the longest of 16/8/4/2 planes that still gives the 768 workgroup slots
+  // (3 per CU) most of a round; each segment stages two halo planes on top of its own
+  const long cols = (long)p.B * p.nty * p.ntx;
+  int zseg = 16;
+  while (zseg > 2 && cols * dsm_cdiv(p.Do, zseg) < 600) zseg >>= 1;
+  const long nt = cols * dsm_cdiv(p.Do, zseg);
+  DSM_REQUIRE(nt < (1L << 31), DSM_ERR_UNSUPPORTED);
+  const size_t lds = (size_t)10 * 34 * 9 * 16;                   // 47.8 KB
+  hipLaunchKernelGGL(conv3d_cout1_zslide_kernel, dim3((unsigned)nt), dim3(NTHREADS), lds, s, p,
+                     p.w, zseg);
+  return dsm_launch_status();
+}
+
+int launch_cout1(ConvParams p, hipStream_t s) {
+  p.ntx = dsm_cdiv(p.Wo, 32); p.nty = dsm_cdiv(p.Ho, 8);
+  p.ntiles = p.B * p.Do * p.nty * p.ntx;
+  const size_t lds = (size_t)3 * 10 * 34 * 2 * 16;              // CK = 8: 32.6 KB
+  const int blocks = p.ntiles < 1024 ? p.ntiles : 1024;          // 4 workgroups per CU
+  hipLaunchKernelGGL(conv3d_cout1_kernel<8>, dim3(blocks), dim3(NTHREADS), lds, s, p, p.w);
+  return dsm_launch_status();
+}
+
+// KIND_CONV / KIND_DECONV: the variant lists of conv_common.hpp, which make_plan has checked (plan_compiled)
+int launch_mfma(const Plan& pl, const ConvParams& p, hipStream_t s) {
+#define DSM_CASE2D(S_, NT_, TM_, K_, DIL_) \
+  if (pl.kind == KIND_CONV && pl.KZ == 1 && pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.K == K_ && \
+      pl.DIL == DIL_) return run_conv<S_, NT_, TM_, 16, 1, K_, DIL_>(p, s);
+  DSM_CONV2D_VARIANTS(DSM_CASE2D)
+#undef DSM_CASE2D
+  if (pl.KZ == 1) return DSM_ERR_UNSUPPORTED;
+#define DSM_CASE_DECONV(NT_, CK_) \
+  if (pl.kind == KIND_DECONV && pl.NT == NT_ && pl.CK == CK_) return run_deconv<NT_, CK_>(p, s);
+  DSM_DECONV3D_VARIANTS(DSM_CASE_DECONV)
+#undef DSM_CASE_DECONV
+#define DSM_CASE(S_, NT_, TM_, CK_) \
+  if (pl.kind == KIND_CONV && pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.CK == CK_) \
+    return run_conv<S_, NT_, TM_, CK_>(p, s, pl.nsplit);
+  DSM_CONV3D_VARIANTS(DSM_CASE)
+#undef DSM_CASE
+  return DSM_ERR_UNSUPPORTED;
 }
 }  // namespace
 
@@ -1253,17 +1362,18 @@ extern "C" int dsm_conv3d_plan(const dsm_conv3d_args* a, char* buf, int len) {
   Plan pl;
   int rc = make_plan(a, &pl);
   if (rc != DSM_OK) { buf[0] = 0; return rc; }
+  const char* pr = prec_name(pl.pm);
   switch (pl.kind) {
-    case 0:
+    case KIND_CONV:
       if (pl.KZ == 3 && pl.nsplit > 1) snprintf(buf, len, "conv3d_mfma_kernel<S=%d,NT=%d,TM=%d,CK=%d>x%d", pl.S, pl.NT, pl.TM, pl.CK, pl.nsplit);
       else if (pl.KZ == 3) snprintf(buf, len, "conv3d_mfma_kernel<S=%d,NT=%d,TM=%d,CK=%d>", pl.S, pl.NT, pl.TM, pl.CK);
       else snprintf(buf, len, "conv2d_mfma_kernel<S=%d,NT=%d,TM=%d,K=%d,DIL=%d>", pl.S, pl.NT, pl.TM, pl.K, pl.DIL);
       break;
-    case 1: snprintf(buf, len, "deconv3d_mfma_kernel<NT=%d,CK=%d>", pl.NT, pl.CK); break;
-    case 2: snprintf(buf, len, "conv3d_cout1_kernel<CK=%d>", pl.CK); break;
-    case 4: snprintf(buf, len, "conv3d_cout1_zslide_kernel"); break;
-    case 5: {
-      const char* pr = pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16");
+    case KIND_DECONV: snprintf(buf, len, "deconv3d_mfma_kernel<NT=%d,CK=%d>", pl.NT, pl.CK); break;
+    case KIND_COUT1: snprintf(buf, len, "conv3d_cout1_kernel<CK=%d>", pl.CK); break;
+    case KIND_DECONV_COUT1: snprintf(buf, len, "deconv3d_cout1_kernel"); break;
+    case KIND_COUT1_ZS: snprintf(buf, len, "conv3d_cout1_zslide_kernel"); break;
+    case KIND_SPLIT:
       if (pl.KZ == 3 && pl.S == 2) snprintf(buf, len, "conv3d_%s_mfma_kernel<S=2,NT=%d,TM=%d>", pr, pl.NT, pl.TM);
       else if (pl.KZ == 3 && pl.nsplit > 1) snprintf(buf, len, "conv3d_%s_mfma_kernel<NT=%d,TM=%d>x%d", pr, pl.NT, pl.TM, pl.nsplit);
       else if (pl.KZ == 3) snprintf(buf, len, "conv3d_%s_mfma_kernel<NT=%d,TM=%d>", pr, pl.NT, pl.TM);
@@ -1271,14 +1381,11 @@ extern "C" int dsm_conv3d_plan(const dsm_conv3d_args* a, char* buf, int len) {
       else if (pl.nsplit > 1) snprintf(buf, len, "conv2d_%s_mfma_kernel<NT=%d,TM=%d,DIL=%d>x%d", pr, pl.NT, pl.TM, pl.DIL, pl.nsplit);
       else snprintf(buf, len, "conv2d_%s_mfma_kernel<NT=%d,TM=%d,DIL=%d>", pr, pl.NT, pl.TM, pl.DIL);
       break;
-    }
-    case 8: snprintf(buf, len, "conv2d_wide_%s_mfma_kernel<S=%d,N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", pl.S, 32 * pl.NT, pl.nsplit, pl.TM); break;
-    case 10: snprintf(buf, len, "conv2d_k5_%s_mfma_kernel<S=%d,N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", pl.S, 32 * pl.NT, pl.nsplit, pl.TM); break;
-    case 9: snprintf(buf, len, "deconv2d_wide_%s_mfma_kernel<N=%d,KS=%d,units=%d>", pl.pm == 2 ? "f16x2" : "f16", 32 * pl.NT, pl.nsplit, pl.TM); break;
-    case 7: snprintf(buf, len, "conv3d_zs_%s_mfma_kernel%s", pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), a->vol_virtual ? "<vol>" : ""); break;
-    case 6: snprintf(buf, len, "deconv3d_%s%s_mfma_kernel<NT=%d>", pl.zs ? "zs_" : "",
-                     pl.pm == 3 ? "bf16x3" : (pl.pm == 2 ? "f16x2" : "f16"), pl.NT); break;
-    default: snprintf(buf, len, "deconv3d_cout1_kernel"); break;
+    case KIND_DECONV_SPLIT: snprintf(buf, len, "deconv3d_%s%s_mfma_kernel<NT=%d>", pl.zs ? "zs_" : "", pr, pl.NT); break;
+    case KIND_ZS: snprintf(buf, len, "conv3d_zs_%s_mfma_kernel%s", pr, a->vol_virtual ? "<vol>" : ""); break;
+    case KIND_WIDE: case KIND_K5:
+      snprintf(buf, len, "conv2d_%s_%s_mfma_kernel<S=%d,N=%d,KS=%d,units=%d>", pl.kind == KIND_K5 ? "k5" : "wide", pr, pl.S, 32 * pl.NT, pl.nsplit, pl.TM); break;
+    case KIND_WIDE_TR: snprintf(buf, len, "deconv2d_wide_%s_mfma_kernel<N=%d,KS=%d,units=%d>", pr, 32 * pl.NT, pl.nsplit, pl.TM); break;
   }
   return DSM_OK;
 }
@@ -1291,145 +1398,40 @@ extern "C" int dsm_basicblock2d_fwd(const dsm_basicblock2d_args* a, dsm_stream_t
   const int C = a->C;
   const unsigned long xb = 4ul * a->B * a->H * a->W * C;
   DSM_REQUIRE(xb < 0x80000000ul, DSM_ERR_UNSUPPORTED);            // 32-bit offsets, out-of-range marker at 2^31
-  const size_t sec3 = (size_t)C * C * 9 * 4 + bf16x3_section_bytes(C, C, 1, 3);
+  const PackLayout L = pack_layout(C, C, 1, 3);
   BbParams p;
   p.x = (const float*)a->x; p.y = (float*)a->y;
-  p.w1_amax = (const float*)((const char*)a->w1_packed + sec3);
-  p.w2_amax = (const float*)((const char*)a->w2_packed + sec3);
-  p.w1 = (const unsigned char*)a->w1_packed + sec3 + 16;
-  p.w2 = (const unsigned char*)a->w2_packed + sec3 + 16;
+  p.w1_amax = (const float*)((const char*)a->w1_packed + L.f16_amax_at());
+  p.w2_amax = (const float*)((const char*)a->w2_packed + L.f16_amax_at());
+  p.w1 = (const unsigned char*)a->w1_packed + L.f16_planes_at();
+  p.w2 = (const unsigned char*)a->w2_packed + L.f16_planes_at();
   p.scale1 = a->scale1; p.shift1 = a->shift1; p.scale2 = a->scale2; p.shift2 = a->shift2;
   p.x_amax = a->x_amax; p.y_amax = a->y_amax;
   p.B = a->B; p.H = a->H; p.W = a->W; p.C = C; p.relu = a->relu; p.skip = a->no_skip ? 0 : 1; p.ntx = p.nty = p.ntiles = 0;
   p.xbytes = (unsigned)xb;
-  p.wbytes = (unsigned)(f16_section_bytes(C, C, 1, 3) - 16);
+  p.wbytes = (unsigned)L.f16_planes_bytes();
   dsm_clear_stale_error();
   return dsmk::run_basicblock_f16(a->precision == DSM_PREC_F16X2 ? 2 : 1, p, (hipStream_t)stream);
 }
 
 extern "C" size_t dsm_conv3d_workspace_bytes(const dsm_conv3d_args* a) {
   Plan pl;
-  if (make_plan_f32(a, &pl) != DSM_OK || (pl.kind != 8 && pl.kind != 9 && pl.kind != 10) || pl.nsplit <= 1) return 0;
-  return (size_t)pl.nsplit * a->B * a->Ho * a->Wo * a->Cout * sizeof(float);
+  if (make_plan(a, &pl, false) != DSM_OK || !kind_is_wide(pl.kind)) return 0;
+  return wide_workspace_bytes(a, pl);
 }
 
 extern "C" int dsm_conv3d_fwd(const dsm_conv3d_args* a, dsm_stream_t stream) {
   Plan pl;
-  int rc = make_plan(a, &pl);
-  if (rc != DSM_OK) return rc;
-  if (pl.kind == 8 || pl.kind == 9 || pl.kind == 10) {
-    WideParams w;
-    wide2d_units(a, &w);
-    const size_t need = dsm_conv3d_workspace_bytes(a);
-    DSM_REQUIRE(need == 0 || (a->workspace && a->workspace_bytes >= need), DSM_ERR_ARG);
-    DSM_REQUIRE(need == 0 || dsm_aligned16(a->workspace), DSM_ERR_ALIGN);
-    DSM_REQUIRE(a->relu == 0 || a->relu == 1 || a->relu == 2, DSM_ERR_ARG);
-    const int ntaps = pl.kind == 10 ? 25 : 9;
-    // (a 5x5 layer's packed buffer IS its fp16 section; a 3x3 layer's section lies behind the fp32 fragments)
-    const char* sec3 = (const char*)a->w_packed + (pl.kind == 10 ? 0 : (size_t)a->Cin * a->Cout * 9 * 4);
-    w.x = (const float*)a->x; w.w = (const unsigned char*)(sec3 + 16); w.w_amax = (const float*)sec3;
-    w.scale = a->scale; w.shift = a->shift; w.y = (float*)a->y; w.ws = (float*)a->workspace;
-    w.x_amax = a->x_amax; w.y_amax = a->y_amax; w.relu = a->relu ? 1 : 0;
-    w.xbytes = (unsigned)(4ul * a->B * a->Hi * a->Wi * a->Cin);
-    w.wbytes = (unsigned)((size_t)a->Cin * a->Cout * ntaps * 4);
-    int grid = (a->flags >> DSM_CONV_BLOCKS_SHIFT) & 0xffff;      // forced grid: the units are walked in a loop
-    if (grid <= 0 || grid > w.nunits) grid = w.nunits;
-    dsm_clear_stale_error();
-    if (pl.kind == 10) return dsmk::run_conv2d_k5_f16(pl.pm, w, grid, (hipStream_t)stream);
-    return dsmk::run_wide2d_f16(pl.pm, w, grid, pl.kind == 9, (hipStream_t)stream);
-  }
-  ConvParams p;
-  p.x = (const float*)a->x; p.w = (const float*)a->w_packed; p.scale = a->scale;
-  p.x_amax = a->x_amax; p.w_amax = nullptr; p.y_amax = a->y_amax;
-  p.shift = a->shift; p.res = (const float*)a->residual; p.y = (float*)a->y;
-  p.force_blocks = (a->flags >> DSM_CONV_BLOCKS_SHIFT) & 0xffff;
-  p.single_kind = (a->flags & DSM_CONV_NO_ONCE) ? 1 : 0;
-  p.B = a->B; p.Cin = a->Cin; p.Cout = a->Cout;
-  p.Di = a->Di; p.Hi = a->Hi; p.Wi = a->Wi; p.Do = a->Do; p.Ho = a->Ho; p.Wo = a->Wo;
-  p.Dr = a->Dr; p.Hr = a->Hr; p.Wr = a->Wr; p.relu = a->relu;
-  p.ntx = p.nty = p.ntiles = 0;
-  if (pl.kind == 7) {
-    ZsParams z;
-    const size_t n = (size_t)a->Cin * 32 * 27;
-    const char* sec2 = (const char*)a->w_packed + n * 4;
-    const char* sec3 = sec2 + n * 6;
-    z.x = (const float*)a->x; z.scale = a->scale; z.shift = a->shift; z.res = (const float*)a->residual;
-    z.y = (float*)a->y; z.x_amax = a->x_amax; z.y_amax = a->y_amax;
-    z.w_amax = pl.pm == 3 ? nullptr : (const float*)sec3;
-    z.w = (const unsigned char*)(pl.pm == 3 ? sec2 : sec3 + 16);
-    z.wbytes = (unsigned)(pl.pm == 3 ? n * 6 : n * 4);
-    z.B = a->B; z.Cin = a->Cin;
-    z.Di = a->Di; z.Hi = a->Hi; z.Wi = a->Wi; z.Do = a->Do; z.Ho = a->Ho; z.Wo = a->Wo;
-    z.Dr = a->Dr; z.Hr = a->Hr; z.Wr = a->Wr; z.relu = a->relu;
-    z.vol = a->vol_virtual ? 1 : 0; z.vol_mask_left = a->vol_mask_left ? 1 : 0;
-    dsm_clear_stale_error();
-    if (pl.pm == 3) return launch_conv_zs<3>(z, p.force_blocks, (hipStream_t)stream);
-    return dsmk::run_zs_f16(pl.pm, z, p.force_blocks, (hipStream_t)stream);
-  }
-  // 32-bit buffer offsets: make_plan_f32 has refused extents of 4 GiB and more
-  p.xbytes = (unsigned)(4ul * a->B * a->Di * a->Hi * a->Wi * a->Cin);
-  p.wbytes = (unsigned)(4ul * a->Cin * a->Cout * (a->kd ? a->kd : 3) * (a->k ? a->k : 3) * (a->k ? a->k : 3));
+  if (const int rc = make_plan(a, &pl)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  dsm_clear_stale_error();
-  if (pl.kind == 3) {
-    p.ntx = dsm_cdiv(p.Wi, 32); p.nty = dsm_cdiv(p.Hi, 4);
-    const long nt = (long)p.B * p.Di * p.nty * p.ntx;
-    DSM_REQUIRE(nt < (1L << 31), DSM_ERR_UNSUPPORTED);
-    const size_t lds = (size_t)(2 * 5 * 33 * 8 + 27 * 8) * 16;     // 45.7 KB
-    hipLaunchKernelGGL(deconv3d_cout1_kernel, dim3((unsigned)nt), dim3(NTHREADS), lds, s, p);
-    return dsm_launch_status();
+  switch (pl.kind) {
+    case KIND_CONV: case KIND_DECONV: return launch_mfma(pl, conv_params(a), s);
+    case KIND_COUT1: return launch_cout1(conv_params(a), s);
+    case KIND_DECONV_COUT1: return launch_deconv_cout1(conv_params(a), s);
+    case KIND_COUT1_ZS: return launch_cout1_zs(conv_params(a), s);
+    case KIND_SPLIT: case KIND_DECONV_SPLIT: return launch_split(a, pl, s);
+    case KIND_ZS: return launch_zs(a, pl, s);
+    case KIND_WIDE: case KIND_WIDE_TR: case KIND_K5: return launch_wide(a, pl, s);
   }
-  if (pl.kind == 5 || pl.kind == 6) {
-    const int kz = pl.kind == 6 ? 3 : pl.KZ;
-    const char* sec2 = (const char*)a->w_packed + (size_t)a->Cin * a->Cout * kz * 9 * 4;
-    if (pl.pm == 3) {
-      p.w = (const float*)sec2;
-      p.wbytes = (unsigned)bf16x3_section_bytes(a->Cin, a->Cout, kz, 3);
-      return dispatch_split<3>(pl, p, s);
-    }
-    const char* sec3 = sec2 + bf16x3_section_bytes(a->Cin, a->Cout, kz, 3);
-    p.w_amax = (const float*)sec3;
-    p.w = (const float*)(sec3 + 16);
-    p.wbytes = (unsigned)(f16_section_bytes(a->Cin, a->Cout, kz, 3) - 16);
-    return dsmk::run_split_f16(pl, p, s);
-  }
-  if (pl.kind == 4) {
-    p.ntx = dsm_cdiv(p.Wo, 32); p.nty = dsm_cdiv(p.Ho, 8);
-    // z-segment: the longest of 16/8/4/2 planes that still gives the 768 workgroup slots
-    // (3 per CU) most of a round; each segment stages two halo planes on top of its own
-    const long cols = (long)p.B * p.nty * p.ntx;
-    int zseg = 16;
-    while (zseg > 2 && cols * dsm_cdiv(p.Do, zseg) < 600) zseg >>= 1;
-    const long nt = cols * dsm_cdiv(p.Do, zseg);
-    DSM_REQUIRE(nt < (1L << 31), DSM_ERR_UNSUPPORTED);
-    const size_t lds = (size_t)10 * 34 * 9 * 16;                   // 47.8 KB
-    hipLaunchKernelGGL(conv3d_cout1_zslide_kernel, dim3((unsigned)nt), dim3(NTHREADS), lds, s, p,
-                       p.w, zseg);
-    return dsm_launch_status();
-  }
-  if (pl.kind == 2) {
-    p.ntx = dsm_cdiv(p.Wo, 32); p.nty = dsm_cdiv(p.Ho, 8);
-    p.ntiles = p.B * p.Do * p.nty * p.ntx;
-    const size_t lds = (size_t)3 * 10 * 34 * 2 * 16;              // CK = 8: 32.6 KB
-    const int blocks = p.ntiles < 1024 ? p.ntiles : 1024;          // 4 workgroups per CU
-    hipLaunchKernelGGL(conv3d_cout1_kernel<8>, dim3(blocks), dim3(NTHREADS), lds, s, p, p.w);
-    return dsm_launch_status();
-  }
-  // the variant lists of conv_common.hpp, which make_plan has checked (plan_compiled)
-#define DSM_CASE2D(S_, NT_, TM_, K_, DIL_) \
-  if (pl.kind == 0 && pl.KZ == 1 && pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.K == K_ && \
-      pl.DIL == DIL_) return run_conv<S_, NT_, TM_, 16, 1, K_, DIL_>(p, s);
-  DSM_CONV2D_VARIANTS(DSM_CASE2D)
-#undef DSM_CASE2D
-  if (pl.KZ == 1) return DSM_ERR_UNSUPPORTED;
-#define DSM_CASE_DECONV(NT_, CK_) \
-  if (pl.kind == 1 && pl.NT == NT_ && pl.CK == CK_) return run_deconv<NT_, CK_>(p, s);
-  DSM_DECONV3D_VARIANTS(DSM_CASE_DECONV)
-#undef DSM_CASE_DECONV
-#define DSM_CASE(S_, NT_, TM_, CK_) \
-  if (pl.kind == 0 && pl.S == S_ && pl.NT == NT_ && pl.TM == TM_ && pl.CK == CK_) \
-    return run_conv<S_, NT_, TM_, CK_>(p, s, pl.nsplit);
-  DSM_CONV3D_VARIANTS(DSM_CASE)
-#undef DSM_CASE
   return DSM_ERR_UNSUPPORTED;
 }

@@ -23,38 +23,51 @@ struct ConvParams {
   float* y_amax;              // or null: max |y| of this launch is folded in (atomic max of the float bits)
 };
 
-// One place decides the kernel variant; dsm_conv3d_fwd launches it, dsm_conv3d_plan names it.
-// kind: 0 conv, 1 deconv, 2 conv cout1, 3 deconv cout1, 4 conv cout1 z-sliding, 5 conv split (bf16x3 / f16x2 / f16), 6 deconv split,
-//       7 z-sliding conv (Cout = 32, stride 1; conv_zs.hpp), 8 wide 2-D conv (Cout 256 / 512 / 1024; conv_wide2d.hpp),
-//       9 its transposed mode (stride 2; backward-data of the stride-2 wide layers),
-//       10 the 5x5 stride-2 2-D conv (Cout 128 / 256; conv_wide2d.hpp with K = 5, fp16 modes only)
-// zs (kind 6, fp16 modes): the z-sliding transposed convolution (deconv_zs.hpp) instead of deconv_split_kernel
-struct Plan { int kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int pm = 3; int once = 0; int zs = 0; };
+// One place decides the kernel variant; dsm_conv3d_fwd launches it, dsm_conv3d_plan names it.  (DESIGN.md and
+// the tests call the kinds by number: "kind 8".)
+enum Kind : int {
+  KIND_CONV = 0,           // fp32-input MFMA convolution
+  KIND_DECONV = 1,         // ... transposed
+  KIND_COUT1 = 2,          // conv cout1
+  KIND_DECONV_COUT1 = 3,   // deconv cout1
+  KIND_COUT1_ZS = 4,       // conv cout1 z-sliding
+  KIND_SPLIT = 5,          // conv split (bf16x3 / f16x2 / f16)
+  KIND_DECONV_SPLIT = 6,   // deconv split
+  KIND_ZS = 7,             // z-sliding conv (Cout = 32, stride 1; conv_zs.hpp)
+  KIND_WIDE = 8,           // wide 2-D conv (Cout 256 / 512 / 1024; conv_wide2d.hpp)
+  KIND_WIDE_TR = 9,        // its transposed mode (stride 2; backward-data of the stride-2 wide layers)
+  KIND_K5 = 10,            // the 5x5 stride-2 2-D conv (Cout 128 / 256; conv_wide2d.hpp with K = 5, fp16 modes only)
+};
+constexpr bool kind_is_wide(Kind k) { return k == KIND_WIDE || k == KIND_WIDE_TR || k == KIND_K5; }
+constexpr bool kind_scales_operands(Kind k) { return k >= KIND_SPLIT; }      // reads x_amax in the fp16 modes
+constexpr bool kind_bounds_own_extents(Kind k) { return k >= KIND_ZS; }      // the others: make_plan's 4 GiB bound
+// zs (KIND_DECONV_SPLIT, fp16 modes): the z-sliding transposed convolution (deconv_zs.hpp) instead of deconv_split_kernel
+struct Plan { Kind kind; int S, NT, TM, CK; int KZ, K, DIL; int nsplit = 1; int pm = 3; int once = 0; int zs = 0; };
 
 // The compiled variants of the kernels that exist in several instantiations.  Each list is expanded twice:
 // into plan_compiled() below, which make_plan consults, and into the chain of launches of its kind
-// (dsm_conv3d_fwd for kinds 0 / 1, dispatch_split for kind 5) -- a plan that make_plan returns therefore
+// (launch_mfma for KIND_CONV / KIND_DECONV, dispatch_split for KIND_SPLIT) -- a plan that make_plan returns therefore
 // launches, and a variant missing here is DSM_ERR_UNSUPPORTED from the plan query and the launch alike.
-// kind 0, 2-D (KZ = 1; 16-channel chunks): (S, NT, TM, K, DIL)
+// KIND_CONV, 2-D (KZ = 1; 16-channel chunks): (S, NT, TM, K, DIL)
 #define DSM_CONV2D_VARIANTS(X) \
   X(1, 1, 1, 3, 1) X(1, 1, 2, 3, 1) X(1, 2, 1, 3, 1) X(1, 4, 1, 3, 1) X(1, 4, 1, 3, 2) \
   X(2, 1, 1, 3, 1) X(2, 2, 1, 3, 1) X(1, 1, 1, 1, 1) X(1, 4, 1, 1, 1) X(2, 2, 1, 1, 1)
-// kind 0, 3-D: (S, NT, TM, CK); the N-split forms (nsplit > 1) are the NT = 1, TM = 1 variants
+// KIND_CONV, 3-D: (S, NT, TM, CK); the N-split forms (nsplit > 1) are the NT = 1, TM = 1 variants
 #define DSM_CONV3D_VARIANTS(X) \
   X(1, 1, 2, 16) X(1, 1, 1, 16) X(1, 2, 2, 8) X(1, 2, 1, 16) X(1, 4, 1, 16) X(2, 1, 1, 8) X(2, 2, 1, 8) X(2, 4, 1, 8)
-// kind 1: (NT, CK)
+// KIND_DECONV: (NT, CK)
 #define DSM_DECONV3D_VARIANTS(X) X(1, 16) X(2, 16)
-// kind 5 at stride 1, every precision mode: (NT, TM, KZ, DIL, NSPLIT).  (Stride 2 is <NT=2,TM=1> alone; the
+// KIND_SPLIT at stride 1, every precision mode: (NT, TM, KZ, DIL, NSPLIT).  (Stride 2 is <NT=2,TM=1> alone; the
 // single-tile `once` form is <1, 2, 1, 1, 2> with 64 inputs in the fp16 modes.)
 #define DSM_SPLIT_VARIANTS(X) \
   X(1, 4, 3, 1, 1) X(1, 2, 3, 1, 1) X(2, 2, 3, 1, 1) X(2, 1, 3, 1, 1) \
   X(1, 4, 1, 1, 1) X(1, 2, 1, 1, 1) X(2, 2, 1, 1, 1) X(2, 1, 1, 1, 1) X(4, 2, 1, 1, 1) X(4, 2, 1, 2, 1) \
   X(1, 2, 1, 1, 2) X(2, 2, 1, 1, 2) X(1, 1, 3, 1, 2) X(1, 1, 3, 1, 4)
 
-// Is the kernel variant that `pl` selects compiled?  (Kinds 2, 3, 4, 7, 8, 9, 10 are single kernels.)
+// Is the kernel variant that `pl` selects compiled?  (The kinds without a case are single kernels.)
 inline bool plan_compiled(const Plan& pl) {
   switch (pl.kind) {
-    case 0:
+    case KIND_CONV:
       if (pl.KZ == 1) {
         if (pl.nsplit != 1 || pl.CK != 16) return false;
 #define DSM_X(S_, NT_, TM_, K_, DIL_) \
@@ -68,13 +81,13 @@ inline bool plan_compiled(const Plan& pl) {
       DSM_CONV3D_VARIANTS(DSM_X)
 #undef DSM_X
       return false;
-    case 1:
+    case KIND_DECONV:
 #define DSM_X(NT_, CK_) if (pl.S == 2 && pl.NT == NT_ && pl.TM == 1 && pl.CK == CK_) return true;
       DSM_DECONV3D_VARIANTS(DSM_X)
 #undef DSM_X
       return false;
-    case 5:
-      // the stride-2, `once` and kind-6 forms are no list: these three lines and the head of dispatch_split
+    case KIND_SPLIT:
+      // the stride-2, `once` and KIND_DECONV_SPLIT forms are no list: these three lines and the head of dispatch_split
       // (conv_split.hpp) are written by hand and must say the same (`once` is set from Cin == 64 only, which
       // the launch checks again); the name table of tests/test_conv_plans.py holds both to the launch
       if (pl.S == 2) return pl.NT == 2 && pl.TM == 1 && pl.KZ == 3 && pl.DIL == 1 && pl.nsplit == 1;
@@ -84,7 +97,7 @@ inline bool plan_compiled(const Plan& pl) {
       DSM_SPLIT_VARIANTS(DSM_X)
 #undef DSM_X
       return false;
-    case 6: return pl.NT == 1 || pl.NT == 2;
+    case KIND_DECONV_SPLIT: return pl.NT == 1 || pl.NT == 2;
     default: return true;
   }
 }
@@ -172,17 +185,12 @@ inline bool wide2d_geometry(WideParams& p) {
   return best >= 0;
 }
 __attribute__((visibility("hidden"))) int run_wide2d_f16(int pm, const WideParams& p, int grid, int transposed, hipStream_t s);
-__attribute__((visibility("hidden"))) int run_conv2d_k5_f16(int pm, const WideParams& p, int grid, hipStream_t s);
 
 }  // namespace dsmk
 
 namespace {
 
-using dsmk::ConvParams;
-using dsmk::Plan;
-using dsmk::ZsParams;
-using dsmk::BbParams;
-using dsmk::WideParams;
+using namespace dsmk;      // the structs, Kind and its enumerators, the run_* entry points
 
 constexpr int NTHREADS = 256;
 

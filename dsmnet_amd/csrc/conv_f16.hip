@@ -28,7 +28,7 @@ int dsmk::run_zs_f16(int pm, const ZsParams& p, int grid, hipStream_t s) {
 }
 
 int dsmk::run_split_f16(const Plan& pl, const ConvParams& p, hipStream_t s) {
-  if (pl.kind == 6 && pl.zs) return pl.pm == 2 ? run_deconv_zs<2>(p, s) : run_deconv_zs<1>(p, s);
+  if (pl.kind == KIND_DECONV_SPLIT && pl.zs) return pl.pm == 2 ? run_deconv_zs<2>(p, s) : run_deconv_zs<1>(p, s);
   if (pl.pm == 2) return dispatch_split<2>(pl, p, s);
   if (pl.pm == 1) return dispatch_split<1>(pl, p, s);
   return DSM_ERR_UNSUPPORTED;
@@ -40,19 +40,10 @@ int dsmk::run_basicblock_f16(int pm, const BbParams& p, hipStream_t s) {
   return DSM_ERR_UNSUPPORTED;
 }
 
+// the window (3 | 5) and the transposed mode are template arguments of the kernel
 int dsmk::run_wide2d_f16(int pm, const WideParams& p, int grid, int transposed, hipStream_t s) {
-  if (transposed) {
-    if (pm == 2) return launch_conv_wide2d<2, true>(p, grid, s);
-    if (pm == 1) return launch_conv_wide2d<1, true>(p, grid, s);
-    return DSM_ERR_UNSUPPORTED;
-  }
-  if (pm == 2) return launch_conv_wide2d<2>(p, grid, s);
-  if (pm == 1) return launch_conv_wide2d<1>(p, grid, s);
-  return DSM_ERR_UNSUPPORTED;
-}
-
-int dsmk::run_conv2d_k5_f16(int pm, const WideParams& p, int grid, hipStream_t s) {
-  if (pm == 2) return launch_conv_wide2d<2, false, 5>(p, grid, s);
-  if (pm == 1) return launch_conv_wide2d<1, false, 5>(p, grid, s);
-  return DSM_ERR_UNSUPPORTED;
+  if (pm != 2 && pm != 1) return DSM_ERR_UNSUPPORTED;
+  if (transposed) return pm == 2 ? launch_conv_wide2d<2, true>(p, grid, s) : launch_conv_wide2d<1, true>(p, grid, s);
+  if (p.K == 3) return pm == 2 ? launch_conv_wide2d<2>(p, grid, s) : launch_conv_wide2d<1>(p, grid, s);
+  return pm == 2 ? launch_conv_wide2d<2, false, 5>(p, grid, s) : launch_conv_wide2d<1, false, 5>(p, grid, s);
 }

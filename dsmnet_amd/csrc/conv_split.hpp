@@ -1105,12 +1105,12 @@ int run_deconv_split(ConvParams p, hipStream_t s) {
   return launch_tiles<deconv_split_kernel<PM, NT>>(p, C::LDS, s, 256 * C::WGS);
 }
 
-// plan kinds 5 (convolution) and 6 (transposed convolution) at precision mode PM
+// KIND_SPLIT (convolution) and KIND_DECONV_SPLIT (transposed convolution) at precision mode PM
 template <int PM>
 int dispatch_split(const Plan& pl, const ConvParams& p, hipStream_t s) {
-  // hand-written up to the list below: keep in step with plan_compiled (conv_common.hpp, kinds 5 / 6)
-  if (pl.kind == 6) return pl.NT == 1 ? run_deconv_split<PM, 1>(p, s) : run_deconv_split<PM, 2>(p, s);
-  if (pl.kind != 5) return DSM_ERR_UNSUPPORTED;
+  // hand-written up to the list below: keep in step with plan_compiled (conv_common.hpp)
+  if (pl.kind == KIND_DECONV_SPLIT) return pl.NT == 1 ? run_deconv_split<PM, 1>(p, s) : run_deconv_split<PM, 2>(p, s);
+  if (pl.kind != KIND_SPLIT) return DSM_ERR_UNSUPPORTED;
   if (pl.S == 2) {
     if constexpr (PM != 3) { if (!p.single_kind) return run_conv_s2<PM>(p, s); }
     return run_conv_split<PM, 2, 1, 3, 1, 2>(p, s);

@@ -252,7 +252,8 @@ typedef struct dsm_conv3d_args {
    * every tensor by a power of two taken from its absolute maximum: `x_amax` points at a device
    * float holding max |x| (or an upper bound of it) -- written by the launch that produced x
    * through ITS y_amax, or by dsm_absmax; required when precision != DSM_PREC_F32 and the layer runs
-   * on a split kernel (dsm_conv3d_plan names it "..._f16x2_..." / "..._f16_..."), ignored otherwise. */
+   * on a split kernel (dsm_conv3d_plan names it "..._f16x2_..." / "..._f16_..."), ignored otherwise.
+   * The names are a contract: the Python host layer decides from them whether to hand x_amax over. */
   int          precision;
   const float* x_amax;
   /* ABI v6: optional.  max |y| of this launch is folded into *y_amax with an atomic maximum on the

@@ -2,7 +2,7 @@
 variant it can launch.
 
 ``dsm_conv3d_plan`` is host-only and shares its selection with the launch and with ``dsm_conv3d_workspace_bytes``
-(one ``make_plan``; the compiled variants are the lists of csrc/conv_common.hpp, from which the launch chains are
+(one ``make_plan`` over one ``select_kernel``; the compiled variants are the lists of csrc/conv_common.hpp, from which the launch chains are
 generated and which the plan consults), so a row that lands on a name here is a set of arguments whose launch
 runs that kernel: tests/test_conv_plans_gpu.py imports ``CASES`` and launches every row against float64.  Pointers are fake addresses (16: aligned), never dereferenced.
 
@@ -14,8 +14,10 @@ runs that kernel: tests/test_conv_plans_gpu.py imports ``CASES`` and launches ev
   tests/test_wide2d_plans.py; the mirror check adds wide points of its own).
 * ``REFUSED``: argument sets whose variant is not compiled.  The plan must say DSM_ERR_UNSUPPORTED, as the launch
   does (before the variant lists were shared the plan answered OK with the name of a kernel that does not exist).
-* the Python mirrors of the planner -- ``costvolume._split_kernel_layer``, ``costvolume._CONV2D_VARIANTS``,
-  ``blocks2d.fused_ok`` -- agree with it on every point of the sweep."""
+* the host layer's questions to the planner -- ``costvolume._split_kernel_layer`` (is the launch handed ``x_amax``),
+  ``costvolume.conv2d_variant`` and ``blocks2d.fused_ok`` (is there a kernel for a 2-D layer) -- are answered by
+  ``dsm_conv3d_plan`` itself, with stand-in addresses and on a copy of the struct; they agree with the plan on every
+  point of the sweep, and the 2-D layers that have a kernel are pinned as a set."""
 import collections
 import ctypes
 import itertools
@@ -314,6 +316,25 @@ def test_split_kernel_layer_mirrors_the_plan(hip_lib, swept):
         assert cv._split_kernel_layer(a) == split, (name, what)
 
 
+def test_split_kernel_layer_asks_with_a_copy_and_needs_no_x_amax(hip_lib):
+    """The launch path asks before it has an ``x_amax``: the struct it hands over comes back untouched, and the
+    answer is the one a stand-in maximum gives."""
+    from dsmnet_amd import costvolume as cv
+    for row in CASES:
+        a, b = row_args(row), row_args(row)
+        a.x_amax = None
+        before = bytes(a)
+        assert cv._split_kernel_layer(a) == cv._split_kernel_layer(b) == ("_f16x2_" in row.name or "_f16_" in row.name)
+        assert bytes(a) == before and a.x_amax is None
+
+
+def test_split_kernel_layer_is_false_for_a_refused_plan(hip_lib):
+    from dsmnet_amd import costvolume as cv
+    for mode, cin, cout, size, stride, k, dil, flags in REFUSED:
+        a = make_args(mode, cin, cout, size, 1, stride, 0, k, dil, flags)
+        assert plan(hip_lib, a)[0] == -2 and cv._split_kernel_layer(a) is False
+
+
 @pytest.mark.parametrize("mode", list(PREC))
 def test_fused_ok_and_the_variant_set_mirror_the_plan(hip_lib, mode):
     from dsmnet_amd import blocks2d, costvolume as cv
@@ -329,4 +350,6 @@ def test_fused_ok_and_the_variant_set_mirror_the_plan(hip_lib, mode):
             assert cv.conv2d_variant(cout, s, k, dil) == ok
             if ok:
                 ok_keys.add((s, cout // 32, k, dil))
-    assert ok_keys == cv._CONV2D_VARIANTS
+    # (stride, Cout / 32, k, dilation) of the 2-D layers that have a kernel, the same in every precision mode
+    assert ok_keys == {(1, 1, 3, 1), (1, 2, 3, 1), (1, 4, 3, 1), (1, 4, 3, 2), (2, 1, 3, 1),
+                       (2, 2, 3, 1), (1, 1, 1, 1), (1, 4, 1, 1), (2, 2, 1, 1)}

@@ -9,7 +9,7 @@ offsets, an out-of-range marker at 2^31.  The host code switches kernels on byte
 * ``EXTENT_ROWS``: the largest extent that still passes and the first one that does not, with the exact plan name
   or DSM_ERR_UNSUPPORTED on each side.  Pointers are fake (16: aligned, never dereferenced); for a refused row
   ``dsm_conv3d_fwd`` must return what ``dsm_conv3d_plan`` does (it returns before any launch);
-* ``costvolume.basicblock2d_ok`` / ``_split_kernel_layer``: the Python mirrors on the same rows;
+* ``costvolume.basicblock2d_ok`` (a Python mirror) / ``_split_kernel_layer`` (asks the plan) on the same rows;
 * the window finder on the shapes of every GPU case, the windowed float64 reference against the full one.
 
 The shapes are products of the prime factors of 2^k - 1: (1, 47, 178481) is 2^23 - 1 voxels, (1, 4095, 4097)
