@@ -88,6 +88,16 @@ DSM_COLOR_JITTER, DSM_COLOR_LIGHTING, DSM_COLOR_NORMALIZE = 1, 2, 4
 DSM_COLOR_MAX_RECORDS = 64
 
 
+class SpatialRecord(ctypes.Structure):
+    """struct dsm_spatial_record (include/dsmnet_hip.h), 48 bytes."""
+    _fields_ = [("shift", c_int), ("ws", c_int), ("hs", c_int), ("w", c_int), ("h", c_int),
+                ("resize", c_int), ("scale_rand", ctypes.c_float), ("pad_", c_int),
+                ("scale_x", ctypes.c_double), ("scale_y", ctypes.c_double)]
+
+
+DSM_SPATIAL_MAX_RECORDS = 48
+
+
 # name -> (restype, argtypes); must list every symbol declared in dsmnet_hip.h
 SIGNATURES = {
     "dsm_abi_version": (c_int, []),
@@ -141,6 +151,7 @@ SIGNATURES = {
     "dsm_suploss_fwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4),
     "dsm_suploss_bwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
     "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),
+    "dsm_stereo_spatial": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SpatialRecord)] + [c_int] * 8 + [c_void_p]),
     "dsm_concat_conv_fwd": (c_int, [c_void_p] * 5 + [c_size_t] + [c_void_p] * 2 + [c_int] * 9 + [c_void_p]),
 }
 

@@ -1986,3 +1986,45 @@ def stereo_color(x, records, alpha, groups):
                                           B, C, H, W, groups, _stream())
     _lib.check(rc, "dsm_stereo_color")
     return x
+
+
+# ----------------------------------------------------------------------------
+# Stereo spatial augmentation + ToTensor (csrc/spatial.hip)
+# ----------------------------------------------------------------------------
+def stereo_spatial(x, records, out_hw, to_tensor_channels=6):
+    """The (B,C,h,w) training batch of the (B,H0,W0,C) channels-last frames ``x`` (imL | imR
+    [| dispL [| dispR]], 6 <= C <= 8): myTransforms.Spatial_stereo's shift, crop and optional
+    linear resize, then ToTensor_numpy's transpose and / 255 of the first ``to_tensor_channels``
+    (0 or 6) planes (csrc/spatial.hip; myTransforms/aug_spatial.py:7-88, aug_color.py:15-26).
+    ``records``: B tuples ``(shift, ws, hs, w, h, resize, scale_rand, scale_x, scale_y)``, the
+    source window in the shifted frame (``dsmnet_amd.transforms`` draws them); ``out_hw`` =
+    (h, w) of the output.  ``x`` is not modified.  One launch per 48 records, on the current
+    stream, no host synchronisation.  Returns the new batch."""
+    if not x.is_cuda:
+        _require_device("stereo_spatial", x)
+    if x.dtype != torch.float32:
+        raise ValueError("stereo_spatial: x must be float32, got %s" % x.dtype)
+    if x.dim() != 4 or not 6 <= x.shape[3] <= 8:
+        raise ValueError("stereo_spatial: x must be (B, H0, W0, C) channels last with 6 <= C <= 8, got %s"
+                         % (tuple(x.shape),))
+    if not x.is_contiguous():
+        raise ValueError("stereo_spatial: x must be a dense (B, H0, W0, C) tensor (not a strided view)")
+    if to_tensor_channels not in (0, 6):
+        raise ValueError("stereo_spatial: to_tensor_channels must be 0 or 6, got %r" % (to_tensor_channels,))
+    B, H0, W0, C = x.shape
+    h, w = int(out_hw[0]), int(out_hw[1])
+    if B < 1 or h < 1 or w < 1:
+        raise ValueError("stereo_spatial: empty batch or output (B = %d, out_hw = %s)" % (B, (h, w)))
+    if len(records) != B:
+        raise ValueError("stereo_spatial: %d records for %d images" % (len(records), B))
+    recs = (_lib.SpatialRecord * B)()
+    for r, (shift, ws, hs, rw, rh, resize, scale_rand, scale_x, scale_y) in zip(recs, records):
+        r.shift, r.ws, r.hs, r.w, r.h = int(shift), int(ws), int(hs), int(rw), int(rh)
+        r.resize, r.scale_rand = int(bool(resize)), float(scale_rand)
+        r.scale_x, r.scale_y = float(scale_x), float(scale_y)
+    y = torch.empty(B, C, h, w, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device), _timed("stereo_spatial_kernel", 8.0 * B * C * h * w):
+        rc = _lib.load().dsm_stereo_spatial(_p(x), _p(y), recs, B, B, C, H0, W0, h, w,
+                                            int(to_tensor_channels), _stream())
+    _lib.check(rc, "dsm_stereo_spatial")
+    return y

@@ -681,6 +681,42 @@ typedef struct dsm_color_record {
 int dsm_stereo_color(void* x, const void* alpha, const dsm_color_record* recs, int n_recs, int B, int C,
                      int H, int W, int groups, dsm_stream_t stream);
 
+/* (ABI v7, additive) Stereo spatial augmentation and ToTensor of a training batch, fused -- replaces
+ * myTransforms/aug_spatial.py:7-88 Spatial_stereo (random shift of the right view, random crop,
+ * optional random scale through cv2.resize, linear) followed by aug_color.py:15-26 ToTensor_numpy.
+ *   x  (B, H0, W0, C) fp32 frames, channels last: imL(0:3) | imR(3:6) [| dispL(6) [| dispR(7)]],
+ *      6 <= C <= 8; NOT modified (the reference shifts its input in place)
+ *   y  (B, C, h, w) dense fp32, fully overwritten
+ * One record per image, drawn on the host.  In the frame shifted by `shift` (channels 3..5 and 7
+ * read `shift` columns to the right; channels >= 6 get += shift where their value is != 0; width
+ * W0 - shift) the source window is [hs, hs + rec.h) x [ws, ws + rec.w).
+ *   resize == 0  y = the window, which must be h x w;
+ *   resize == 1  y = the window resized to (w, h) by cv2's linear rule: for output column dx,
+ *                fx = (float)((dx + 0.5) * scale_x - 0.5) (fp64 inside), sx = floor(fx), fx -= sx;
+ *                sx < 0: sx = 0, fx = 0; sx >= rec.w - 1: sx = rec.w - 1, fx = 0; second tap
+ *                min(sx + 1, rec.w - 1); rows alike with scale_y, rec.h.  fp32, no contraction:
+ *                horizontal S[sx]*(1-fx) + S[sx+1]*fx on both rows, then the same form vertically.
+ *                Channels >= 6 are then multiplied by scale_rand.
+ * Last, channels < to_tensor_channels (0 or 6) are divided by 255.
+ * DSM_ERR_ARG (nothing launched): null pointers, C outside 6..8, n_recs != B, shift outside
+ * [0, W0), a window outside [0, W0 - shift) x [0, H0), a resize == 0 window that is not h x w,
+ * a scale that is not finite and positive.  DSM_ERR_UNSUPPORTED: one image of x or y with 2^31
+ * elements or more.  DSM_ERR_ALIGN: x or y not 4-byte aligned.  Records travel in kernel
+ * arguments, up to DSM_SPATIAL_MAX_RECORDS per launch (larger batches: one launch per chunk); no
+ * host synchronisation.  sizeof(dsm_spatial_record) == 48. */
+#define DSM_SPATIAL_MAX_RECORDS 48
+typedef struct dsm_spatial_record {
+  int shift;
+  int ws, hs, w, h;
+  int resize;
+  float scale_rand;
+  int pad_;
+  double scale_x, scale_y;
+} dsm_spatial_record;
+
+int dsm_stereo_spatial(const void* x, void* y, const dsm_spatial_record* recs, int n_recs, int B, int C,
+                       int H0, int W0, int h, int w, int to_tensor_channels, dsm_stream_t stream);
+
 /* (ABI v7, additive) First convolution of a concatenation cost volume, from 2-D maps (csrc/sepvol.hip,
  * DESIGN.md 3.2f): y = relu?(conv3d(volume, W; k3 s1 p1) * scale + shift) for the volume of
  * dsm_concat_volume_fwd, which is never formed -- plane d is [left | right shifted by d], so the
