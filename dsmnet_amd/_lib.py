@@ -67,7 +67,11 @@ class SelfsupItem(ctypes.Structure):
                 ("B", c_int), ("h", c_int), ("w", c_int), ("H0", c_int), ("W0", c_int),
                 ("left", c_int), ("top", c_int), ("scale_factor", c_int),
                 ("delt_im", ctypes.c_float), ("delt_disp", ctypes.c_float), ("weight", ctypes.c_float),
-                ("pad_", c_int)]
+                ("ds_divisor", c_int)]
+
+
+# the flags word of dsm_selfsup_fwd / dsm_selfsup_bwd (include/dsmnet_hip.h)
+DSM_SELFSUP_MASK, DSM_SELFSUP_CAP, DSM_SELFSUP_DS, DSM_SELFSUP_LR = 1, 2, 4, 8
 
 
 class SuplossItem(ctypes.Structure):

@@ -1701,8 +1701,22 @@ class DecoderCatFunction(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------
-# Self-supervised depthmono[-mask] pyramid loss (csrc/selfsup.hip)
+# Self-supervised depthmono[-mask] and Cap[_ds][_lr][-mask] pyramid loss (csrc/selfsup.hip)
 # ----------------------------------------------------------------------------
+_SELFSUP_TERMS = {"ds": _lib.DSM_SELFSUP_DS, "lr": _lib.DSM_SELFSUP_LR}
+
+
+def _selfsup_flags(spec):
+    """The flags word of dsm_selfsup_fwd / _bwd and the ``_timed`` label suffix of the objective."""
+    flags = _lib.DSM_SELFSUP_MASK if spec["flag_mask"] else 0
+    if spec["objective"] == "depthmono":
+        return flags, ""
+    flags |= _lib.DSM_SELFSUP_CAP
+    for t in spec["terms"]:
+        flags |= _SELFSUP_TERMS[t]
+    return flags, "_cap" + "".join("_" + t for t in ("ds", "lr") if t in spec["terms"])
+
+
 def _int_strides(name, t):
     st = t.stride()
     if any(s < 0 or s >= 2 ** 31 for s in st) or t.numel() >= 2 ** 31:
@@ -1740,6 +1754,7 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
                 it.scale_factor = int(sf)
                 it.delt_im, it.delt_disp = float(spec["delts"][p][di]), float(spec["delts"][p][dd])
                 it.weight = float(spec["weights"][p])
+                it.ds_divisor = int(spec["ds_divisors"][p])
         return items
 
     @staticmethod
@@ -1753,9 +1768,12 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
         ws = torch.empty(nf, device=imL.device, dtype=torch.float32)
         loss = torch.empty((), device=imL.device, dtype=torch.float32)
         aux = torch.empty(4 * len(items), device=imL.device, dtype=torch.float32)
-        with torch.cuda.device(imL.device), _timed("selfsup_fwd", 4.0 * nf):
-            rc = lib.dsm_selfsup_fwd(items, len(items), int(bool(spec["flag_mask"])), _p(ws), _p(loss),
-                                     _p(aux), _stream())
+        flags, tag = _selfsup_flags(spec)
+        # both objectives enter the library once for two kernels; depthmono keeps the label under which
+        # its timings are on record, Cap's names the kernels "+"-joined, as suploss's does
+        label = "selfsup%s_fwd%s" % (tag, "_tiles+reduce" if tag else "")
+        with torch.cuda.device(imL.device), _timed(label, 4.0 * nf):
+            rc = lib.dsm_selfsup_fwd(items, len(items), flags, _p(ws), _p(loss), _p(aux), _stream())
         _lib.check(rc, "dsm_selfsup_fwd")
         ctx.spec = spec
         ctx.save_for_backward(imL, imR_src, imL1, imR1_src, ws, aux, *disps)
@@ -1766,24 +1784,30 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
     def backward(ctx, gloss, gaux):
         saved = ctx.saved_tensors
         imgs, ws, aux, disps = saved[:4], saved[4], saved[5], saved[6:]
-        flat = torch.zeros(sum(d.numel() for d in disps), device=ws.device, dtype=torch.float32)
+        flags, tag = _selfsup_flags(ctx.spec)
+        # with the lr term the kernel accumulates (the other view scatters in); without it every
+        # element is stored by its one writer, so the buffer needs no fill launch
+        scatter = not (flags & _lib.DSM_SELFSUP_CAP) or bool(flags & _lib.DSM_SELFSUP_LR)
+        flat = (torch.zeros if scatter else torch.empty)(sum(d.numel() for d in disps), device=ws.device,
+                                                         dtype=torch.float32)
         grads, o = [], 0
         for d in disps:
             grads.append(flat[o:o + d.numel()].view(d.shape))
             o += d.numel()
         items = SelfsupPyramidLossFunction._items(ctx.spec, imgs, disps, grads)
         g = gloss.to(torch.float32).contiguous()
-        with torch.cuda.device(ws.device), _timed("selfsup_bwd", 4.0 * (ws.numel() + 2 * flat.numel())):
-            rc = _lib.load().dsm_selfsup_bwd(items, len(items), int(bool(ctx.spec["flag_mask"])), _p(ws),
-                                             _p(aux), _p(g), _stream())
+        label = "selfsup%s_bwd%s" % (tag, "" if scatter else "_gather")
+        with torch.cuda.device(ws.device), _timed(label, 4.0 * (ws.numel() + 2 * flat.numel())):
+            rc = _lib.load().dsm_selfsup_bwd(items, len(items), flags, _p(ws), _p(aux), _p(g), _stream())
         _lib.check(rc, "dsm_selfsup_bwd")
         return (None, None, None, None, None) + tuple(grads)
 
 
 def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1, dispL1s, levels,
-                         weights, factors, flag_mask, delts, return_aux=False):
-    """The reference's depthmono[-mask] objective over a disparity pyramid in three launches
-    forward and two backward (csrc/selfsup.hip; losses/loss.py:196-236, 393-405, 424-467,
+                         weights, factors, flag_mask, delts, return_aux=False, objective="depthmono",
+                         terms=("ds", "lr"), ds_divisors=None):
+    """The reference's depthmono[-mask] objective over a disparity pyramid in two launches forward
+    (tiles, reduce) and two backward (the gradient buffer's fill, tiles) (csrc/selfsup.hip; losses/loss.py:196-236, 393-405, 424-467,
     losses/SSIM.py, utils/imwrap.py:37-72):
 
         sum_p weights[p] * (loss_depthmono(imL_k, imwrap(imR_src, dispLs[p], LeftTop=lefttop,
@@ -1794,8 +1818,27 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
     ``imR_src``/``imR1_src`` (B,3,H0,W0) may be strided views; ``dispLs[p]``/``dispL1s[p]``
     (B,1,h_k,w_k) take the gradient.  ``delts[p]`` = the reference's four random epsilons of the
     entry, in its draw order (imL_wrap, imL1_wrap, dispL_wrap, dispL1_wrap).  No host
-    synchronisation.  ``return_aux``: also the (2P,4) per-view [w, fallback, C, simlary]."""
+    synchronisation.  ``return_aux``: also the (2P,4) per-view [w, fallback, C, simlary].
+
+    ``objective="cap"``: loss_Cap_ds_lr (loss.py:238-283) in place of loss_depthmono -- no
+    "< 1024 valid pixels" fallback (no valid pixel: w = 0.001), the terms named in ``terms`` (any
+    of "ds", "lr") only, and the smoothness term weighted w / ``ds_divisors[p]`` (positive
+    integers; None: 1).  The forward is the same two launches.  Without "lr" the backward is ONE
+    gather launch into an unfilled buffer and the gradient is bit-reproducible; with it, the fill
+    and the scatter of depthmono.  depthmono always has
+    both terms and no divisor: ``terms`` and ``ds_divisors`` must be left at their defaults."""
     n = len(dispLs)
+    if objective not in ("depthmono", "cap"):
+        raise ValueError("selfsup_pyramid_loss: objective %r is neither 'depthmono' nor 'cap'" % (objective,))
+    terms = tuple(terms)
+    if any(t not in _SELFSUP_TERMS for t in terms):
+        raise ValueError("selfsup_pyramid_loss: terms %r: only 'ds' and 'lr' exist" % (terms,))
+    if objective == "depthmono" and (set(terms) != {"ds", "lr"} or ds_divisors is not None):
+        raise ValueError("selfsup_pyramid_loss: depthmono has both terms and no ds_divisors")
+    if ds_divisors is None:
+        ds_divisors = [1] * n
+    if len(ds_divisors) != n or any(int(v) != v or int(v) < 1 for v in ds_divisors):
+        raise ValueError("selfsup_pyramid_loss: ds_divisors %r: one integer >= 1 per disparity" % (ds_divisors,))
     if not (len(dispL1s) == len(levels) == len(weights) == len(factors) == len(delts) == n) or n < 1:
         raise ValueError("selfsup_pyramid_loss: one level, weight, factor and delt set per disparity")
     if 2 * n > 16:
@@ -1834,7 +1877,8 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
     spec = {"levels": [int(k) for k in levels], "factors": [int(f) for f in factors],
             "weights": [float(x) for x in weights], "delts": [tuple(float(x) for x in dl) for dl in delts],
             "lefttop": (int(lefttop[0]), int(lefttop[1])), "lefttop1": (int(lefttop1[0]), int(lefttop1[1])),
-            "flag_mask": bool(flag_mask)}
+            "flag_mask": bool(flag_mask), "objective": objective, "terms": terms,
+            "ds_divisors": [int(v) for v in ds_divisors]}
     loss, aux = SelfsupPyramidLossFunction.apply(spec, imL, imR_src, imL1, imR1_src, *ds)
     return (loss, aux.view(2 * n, 4)) if return_aux else loss
 

@@ -28,6 +28,16 @@
 // tap order nw, ne, sw, se, `+ delt` on in-bounds taps only.  The masks follow the PyTorch 0.3
 // meaning: mask2 = (delta < 3) & !(delta < 1), mask_im = (disp_wrap == 0)
 // & mask_ap.  w, the masks and weight_common take no gradient, as in the reference.
+//
+// The "Cap[_ds][_lr][-mask]" objective (loss.py:238-283 loss_Cap_ds_lr) runs on the same kernels:
+// the objective (Cap or depthmono), -mask and the two optional terms are template parameters of
+// the tile kernels, chosen by the flags word (DSM_SELFSUP_*).  Cap differs in three ways: mask_ap
+// has no "< 1024 valid pixels" fallback (so weight_im has one outcome and one saved plane; no
+// valid pixel at all gives w = 0.001, Python's max(0, nan)), the smoothness weight is
+// w / ds_divisor (per item), and C_ds / C_lr are there only when asked for.  Without the lr term
+// nothing flows through disp_wrap: every gradient element has one writer, the backward is a pure
+// gather that STORES every element (no atomics, no zeroed buffer, bit-reproducible), and without
+// -mask the fliplr disparity warp is not computed at all.
 #include "common.hpp"
 
 namespace {
@@ -51,6 +61,9 @@ struct Work {
   int n, flag_mask;
   float* part;                              // tile partial sums [tiles][NPART]
   float* save;                              // [item][NSAVE][B*h*w]
+  // the objective, for the reduction (the tile kernels take it as template parameters); after the
+  // older fields, whose offsets the depthmono instantiation keeps
+  int cap, ds, lr;
 };
 
 __device__ __forceinline__ float sgnf(float v) { return (float)((v > 0.f) - (v < 0.f)); }
@@ -173,6 +186,14 @@ __device__ __forceinline__ void filter_tile(const Work& W, float (*reg)[RW][RW +
   }
 }
 
+// CAP: loss_Cap_ds_lr's rule (no fallback), else loss_depthmono's; MASK: the -mask weights;
+// DS / LR: the smoothness and left-right terms.  depthmono is the ONE instantiation
+// <false, false, true, true>: it has both terms and reads -mask from W.flag_mask at run time, as
+// it always did, so that it compiles to the instructions it had before the Cap rule existed
+template <bool CAP, bool MASK>
+__device__ __forceinline__ bool has_mask(const Work& W) { return CAP ? MASK : W.flag_mask != 0; }
+
+template <bool CAP, bool MASK, bool DS, bool LR>
 __global__ __launch_bounds__(256) void selfsup_fwd_tiles(const Work W) {
   __shared__ float reg[5][RW][RW + 1];
   __shared__ float hs[5][RW][T + 1];
@@ -226,14 +247,14 @@ __global__ __launch_bounds__(256) void selfsup_fwd_tiles(const Work W) {
     const float dS_mu2 = 2.f * mu1 * (A2 - A1) * inv - 2.f * mu2 * S * (1.f / B1 - 1.f / B2);
     const float dS_e22 = -S / B2;
     const float dS_e12 = 2.f * A1 * inv;
-    float dw, ddw;
-    disp_warp(q, d, dw, ddw);
+    float dw = 0.f, ddw;
+    if (!CAP || MASK || LR) disp_warp(q, d, dw, ddw);         // Cap with neither: disp_other is never read
     // mask_ap and the weight switches test exact zeros (a sample with all four taps outside):
     // steps in the loss, so a sample within rounding of the border may fall either way in fp32
     // and fp64 -- the GPU tests bound the fraction of such pixels instead of their error
     const bool valid = iw[0] != 0.f;                          // mask_ap (loss.py:199)
     float wimA = 1.f, wimB = 1.f, wlr = 1.f;
-    if (W.flag_mask) {
+    if (has_mask<CAP, MASK>(W)) {
       const float wc = weight_common(d, dw, it.scale_factor);
       wimA = (dw == 0.f && valid) ? 1.f : wc;                  // mask_im with the real mask_ap
       wimB = (dw == 0.f) ? 1.f : wc;                           // ... with the fallback mask_ap = 1
@@ -245,32 +266,32 @@ __global__ __launch_bounds__(256) void selfsup_fwd_tiles(const Work W) {
     const float* imp = (const float*)it.im + (long)b * it.im_stride[0] + (long)y * it.im_stride[2] +
                        (long)x * it.im_stride[3];
     float ds = 0.f;
-    if (x + 1 < w) {
+    if (DS && x + 1 < w) {
       float e = 0.f;
 #pragma unroll
       for (int c = 0; c < 3; ++c) e += fabsf(imp[(long)c * it.im_stride[1] + it.im_stride[3]] - im[c]);
       ds += fabsf(disp[o + 1] - d) * expf(-e);
     }
-    if (y + 1 < h) {
+    if (DS && y + 1 < h) {
       float e = 0.f;
 #pragma unroll
       for (int c = 0; c < 3; ++c) e += fabsf(imp[(long)c * it.im_stride[1] + it.im_stride[2]] - im[c]);
       ds += fabsf(disp[o + w] - d) * expf(-e);
     }
     part[0] = wimA * ap;
-    part[1] = wimB * ap;
+    if (!CAP) part[1] = wimB * ap;
     part[2] = ds;
-    part[3] = wlr * fabsf(d - dw);
+    if (LR) part[3] = wlr * fabsf(d - dw);
     part[4] = valid ? S : 0.f;
     part[5] = valid ? 1.f : 0.f;
-    part[6] = S;
+    if (!CAP) part[6] = S;
     const long n = (long)it.B * h * w, p = (long)b * h * w + o;
     float* sv = W.save + W.save0[i];
     sv[p] = dS_mu2;
     sv[n + p] = dS_e22;
     sv[2 * n + p] = dS_e12;
-    sv[3 * n + p] = wimA;
-    sv[4 * n + p] = wimB;
+    if (!CAP || MASK) sv[3 * n + p] = wimA;                   // Cap without -mask: weight_im = 1
+    if (!CAP) sv[4 * n + p] = wimB;
   }
   const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
 #pragma unroll
@@ -312,6 +333,24 @@ __global__ __launch_bounds__(256) void selfsup_reduce(const Work W, float* loss,
       const int j = i + s;
       const double n = (double)W.it[j].B * W.it[j].h * W.it[j].w;
       const double count = sums[j][5];
+      if (W.cap) {
+        // loss.py:241-243, 266-277: the mean over mask_ap however few pixels that is.  None at
+        // all: the reference's empty mean is NaN and Python's max(0, nan) is 0, so w = 0.001;
+        // count never divides into anything that reaches the loss
+        const bool any = count > 0.0;
+        const double simlary = any ? sums[j][4] / count : 0.0;
+        const double wt = any ? fmax(0.0, simlary - 0.75) / 2.0 + 0.001 : 0.001;
+        const int dv = W.it[j].ds_divisor > 0 ? W.it[j].ds_divisor : 1;
+        double c = sums[j][0] / (3.0 * n);
+        if (W.ds) c += (sums[j][2] / n) * (wt / (double)dv);
+        if (W.lr) c += (sums[j][3] / n) * wt;
+        C[s] = c;
+        aux[4 * j + 0] = (float)wt;
+        aux[4 * j + 1] = 0.f;
+        aux[4 * j + 2] = (float)c;
+        aux[4 * j + 3] = (float)simlary;
+        continue;
+      }
       const bool fallback = count < 1024.0;                   // loss.py:200-201
       const double simlary = fallback ? sums[j][6] / n : sums[j][4] / count;
       const double wt = fmax(0.0, simlary - 0.75) / 2.0 + 0.001;   // wfun, loss.py:33-34
@@ -327,6 +366,7 @@ __global__ __launch_bounds__(256) void selfsup_reduce(const Work W, float* loss,
   loss[0] = (float)total;
 }
 
+template <bool CAP, bool MASK, bool DS, bool LR>
 __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const float* __restrict__ aux,
                                                          const float* __restrict__ gloss) {
   __shared__ float reg[3][RW][RW + 1];
@@ -340,8 +380,10 @@ __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const flo
   const long n = (long)it.B * h * w;
   const float* sv = W.save + W.save0[i];
   const float wt = aux[4 * i + 0];
-  const bool fallback = aux[4 * i + 1] != 0.f;
+  const bool fallback = !CAP && aux[4 * i + 1] != 0.f;
   const float* wim_plane = sv + (fallback ? 4 : 3) * n;
+  constexpr bool unit_wim = CAP && !MASK;                     // no plane was saved: weight_im = 1
+  const float wds = CAP ? wt / (float)(it.ds_divisor > 0 ? it.ds_divisor : 1) : wt;   // loss.py:272
   const float gs = gloss[0] * it.weight;
   const float inv_n = 1.f / (float)n;
   const float* disp = (const float*)it.disp + (long)b * h * w;
@@ -353,7 +395,7 @@ __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const flo
     float p0 = 0.f, p1 = 0.f, p2 = 0.f;
     if (y >= 0 && y < h && x >= 0 && x < w) {
       const long p = (long)b * h * w + (long)y * w + x;
-      const float wim = wim_plane[p];
+      const float wim = unit_wim ? 1.f : wim_plane[p];
       p0 = wim * sv[p]; p1 = wim * sv[n + p]; p2 = wim * sv[2 * n + p];
     }
     reg[0][ry][rx] = p0; reg[1][ry][rx] = p1; reg[2][ry][rx] = p2;
@@ -369,7 +411,7 @@ __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const flo
   const float d = disp[o];
   float iw[3], div[3], im[3];
   image_warp(W, q, d, iw, div, im);
-  const float wim = wim_plane[p];
+  const float wim = unit_wim ? 1.f : wim_plane[p];
 
   // 2. C_ap: d C / d im_wrap_c, then through the sample position (imwrap.py:67: dix/dd = -W0/(W0-1))
   float gix = 0.f;
@@ -383,19 +425,22 @@ __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const flo
 
   // 3. C_lr = |d - d_wrap| * weight_lr: d is the offset of its own warp and the source of the
   //    other view's warp (scattered there: the other item's d_wrap taps land in this grad_other)
-  float dw, ddw;
-  const Bil t = disp_warp(q, d, dw, ddw);
-  const float wlr = W.flag_mask ? ((dw == 0.f) ? 0.f : weight_common(d, dw, it.scale_factor)) : 1.f;
-  const float s = sgnf(d - dw) * wlr * wt * inv_n;
-  gd += s;
-  gd += -s * ddw * ((float)w / (float)(w - 1));
-  if (s != 0.f) {
-    float* go = (float*)it.grad_other + (long)b * h * w;
-    const float v = -s * gs;
-    if (t.in00) unsafeAtomicAdd(go + (long)t.y0 * w + t.x0, v * (t.wx0 * t.wy0));
-    if (t.in01) unsafeAtomicAdd(go + (long)t.y0 * w + t.x0 + 1, v * (t.wx1 * t.wy0));
-    if (t.in10) unsafeAtomicAdd(go + (long)(t.y0 + 1) * w + t.x0, v * (t.wx0 * t.wy1));
-    if (t.in11) unsafeAtomicAdd(go + (long)(t.y0 + 1) * w + t.x0 + 1, v * (t.wx1 * t.wy1));
+  //    Without the term nothing reaches disp_wrap (the weights are detached): no warp, no scatter
+  if (LR) {
+    float dw, ddw;
+    const Bil t = disp_warp(q, d, dw, ddw);
+    const float wlr = has_mask<CAP, MASK>(W) ? ((dw == 0.f) ? 0.f : weight_common(d, dw, it.scale_factor)) : 1.f;
+    const float s = sgnf(d - dw) * wlr * wt * inv_n;
+    gd += s;
+    gd += -s * ddw * ((float)w / (float)(w - 1));
+    if (s != 0.f) {
+      float* go = (float*)it.grad_other + (long)b * h * w;
+      const float v = -s * gs;
+      if (t.in00) unsafeAtomicAdd(go + (long)t.y0 * w + t.x0, v * (t.wx0 * t.wy0));
+      if (t.in01) unsafeAtomicAdd(go + (long)t.y0 * w + t.x0 + 1, v * (t.wx1 * t.wy0));
+      if (t.in10) unsafeAtomicAdd(go + (long)(t.y0 + 1) * w + t.x0, v * (t.wx0 * t.wy1));
+      if (t.in11) unsafeAtomicAdd(go + (long)(t.y0 + 1) * w + t.x0 + 1, v * (t.wx1 * t.wy1));
+    }
   }
 
   // 4. C_ds1: the pixel is the right end of (x-1, x) and the left end of (x, x+1); same in y
@@ -403,45 +448,76 @@ __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const flo
                      (long)x * it.im_stride[3];
   const int cs = it.im_stride[1], xs = it.im_stride[3], ys = it.im_stride[2];
   float gds = 0.f;
-  if (x + 1 < w) {
+  if (DS && x + 1 < w) {
     float e = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) e += fabsf(imp[(long)c * cs + xs] - im[c]);
     gds -= sgnf(disp[o + 1] - d) * expf(-e);
   }
-  if (x > 0) {
+  if (DS && x > 0) {
     float e = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) e += fabsf(im[c] - imp[(long)c * cs - xs]);
     gds += sgnf(d - disp[o - 1]) * expf(-e);
   }
-  if (y + 1 < h) {
+  if (DS && y + 1 < h) {
     float e = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) e += fabsf(imp[(long)c * cs + ys] - im[c]);
     gds -= sgnf(disp[o + w] - d) * expf(-e);
   }
-  if (y > 0) {
+  if (DS && y > 0) {
     float e = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) e += fabsf(im[c] - imp[(long)c * cs - ys]);
     gds += sgnf(d - disp[o - w]) * expf(-e);
   }
-  gd += gds * wt * inv_n;
-  unsafeAtomicAdd((float*)it.grad_disp + p, gd * gs);
+  gd += gds * wds * inv_n;
+  // with the lr term the other view's scatter lands here too (accumulate into the zeroed buffer);
+  // without it this thread is the element's only writer: a plain store, whatever was there
+  if (LR) unsafeAtomicAdd((float*)it.grad_disp + p, gd * gs);
+  else ((float*)it.grad_disp)[p] = gd * gs;
 }
 
-int make_work(const dsm_selfsup_item* items, int n, int flag_mask, void* workspace, Work& W) {
+template <bool C, bool M, bool D, bool L>
+struct Objective {
+  static constexpr bool cap = C, mask = M, ds = D, lr = L;
+};
+
+// the flags word -> the kernel instantiation; false for a word that names no objective
+template <class F>
+bool with_objective(int flags, F&& f) {
+  switch (flags) {
+    case 0:
+    case DSM_SELFSUP_MASK: f(Objective<false, false, true, true>{}); return true;     // depthmono[-mask]
+#define DSM_CAP_CASE(M, D, L)                                                                   \
+  case DSM_SELFSUP_CAP | (M ? DSM_SELFSUP_MASK : 0) | (D ? DSM_SELFSUP_DS : 0) | (L ? DSM_SELFSUP_LR : 0): \
+    f(Objective<true, M, D, L>{});                                                              \
+    return true;
+    DSM_CAP_CASE(false, false, false) DSM_CAP_CASE(true, false, false)
+    DSM_CAP_CASE(false, true, false) DSM_CAP_CASE(true, true, false)
+    DSM_CAP_CASE(false, false, true) DSM_CAP_CASE(true, false, true)
+    DSM_CAP_CASE(false, true, true) DSM_CAP_CASE(true, true, true)
+#undef DSM_CAP_CASE
+    default: return false;
+  }
+}
+
+int make_work(const dsm_selfsup_item* items, int n, int flags, void* workspace, Work& W) {
   DSM_REQUIRE(items && workspace, DSM_ERR_ARG);
   DSM_REQUIRE(n >= 2 && n <= DSM_SELFSUP_MAX_ITEMS && n % 2 == 0, DSM_ERR_ARG);
+  DSM_REQUIRE(with_objective(flags, [](auto) {}), DSM_ERR_ARG);
   W.n = n;
-  W.flag_mask = flag_mask ? 1 : 0;
+  W.flag_mask = flags & DSM_SELFSUP_MASK;
+  W.cap = (flags & DSM_SELFSUP_CAP) != 0;
+  W.ds = !W.cap || (flags & DSM_SELFSUP_DS);
+  W.lr = !W.cap || (flags & DSM_SELFSUP_LR);
   long tiles = 0, save = 0;
   for (int i = 0; i < n; ++i) {
     const dsm_selfsup_item& it = items[i];
     DSM_REQUIRE(it.im && it.src && it.disp && it.disp_other, DSM_ERR_ARG);
     DSM_REQUIRE(it.B > 0 && it.h > 1 && it.w > 1 && it.H0 > 1 && it.W0 > 1, DSM_ERR_ARG);   // imwrap.py:48
-    DSM_REQUIRE(it.scale_factor > 0 && it.left >= 0 && it.top >= 0, DSM_ERR_ARG);
+    DSM_REQUIRE(it.scale_factor > 0 && it.left >= 0 && it.top >= 0 && it.ds_divisor >= 0, DSM_ERR_ARG);
     if (i % 2 == 1) DSM_REQUIRE(it.B == items[i - 1].B && it.h == items[i - 1].h && it.w == items[i - 1].w, DSM_ERR_ARG);
     W.it[i] = it;
     W.ntx[i] = dsm_cdiv(it.w, T);
@@ -460,10 +536,18 @@ int make_work(const dsm_selfsup_item* items, int n, int flag_mask, void* workspa
   }
   W.tile0[n] = (int)tiles;
   float gf[11], sumf = 0.f;                       // SSIM.py:6-8 (torch normalises in fp32)
+  double sumd = 0.0;
   for (int k = 0; k < 11; ++k) {
     gf[k] = (float)exp(-(k - 5) * (k - 5) / (2.0 * 1.5 * 1.5));
     sumf += gf[k];
+    sumd += gf[k];
   }
+  // torch's fp32 g.sum() is a vectorised sum and lands on the correctly rounded value, one ulp above
+  // this sequential one: the two windows then sum to 1 - 6.9e-8 and 1 + 8.9e-8, which
+  // E[x^2] - mu^2 turns into a one-sided 4e-8 on variances of ~1e-3 and so into a one-sided ~2e-6
+  // on simlary.  Cap's w = (simlary - 0.75) / 2 + 0.001 amplifies that, so Cap takes torch's taps;
+  // depthmono keeps the sequential sum and with it the bits it always gave
+  if (W.cap) sumf = (float)sumd;
   for (int k = 0; k < 11; ++k) W.g[k] = gf[k] / sumf;
   W.part = (float*)workspace;
   W.save = W.part + tiles * NPART;
@@ -483,30 +567,39 @@ extern "C" size_t dsm_selfsup_workspace_floats(const dsm_selfsup_item* items, in
   return f;
 }
 
-extern "C" int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flag_mask, void* workspace,
+extern "C" int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flags, void* workspace,
                                void* loss, void* aux, dsm_stream_t stream) {
   DSM_REQUIRE(loss && aux, DSM_ERR_ARG);
   Work W;
-  const int rc = make_work(items, n_items, flag_mask, workspace, W);
+  const int rc = make_work(items, n_items, flags, workspace, W);
   if (rc != DSM_OK) return rc;
   dsm_clear_stale_error();
-  hipLaunchKernelGGL(selfsup_fwd_tiles, dim3(W.tile0[W.n]), dim3(256), 0, (hipStream_t)stream, W);
+  with_objective(flags, [&](auto o) {
+    using O = decltype(o);
+    hipLaunchKernelGGL((selfsup_fwd_tiles<O::cap, O::mask, O::ds, O::lr>), dim3(W.tile0[W.n]), dim3(256), 0,
+                       (hipStream_t)stream, W);
+  });
   hipLaunchKernelGGL(selfsup_reduce, dim3(1), dim3(256), 0, (hipStream_t)stream, W, (float*)loss,
                      (float*)aux);
   return dsm_launch_status();
 }
 
-extern "C" int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flag_mask,
+extern "C" int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flags,
                                const void* workspace, const void* aux, const void* grad_loss,
                                dsm_stream_t stream) {
   DSM_REQUIRE(aux && grad_loss, DSM_ERR_ARG);
+  // Cap without the lr term: nothing scatters into the other view, grad_other is not needed
+  const bool gather_only = (flags & DSM_SELFSUP_CAP) && !(flags & DSM_SELFSUP_LR);
   for (int i = 0; items && i < n_items && i < DSM_SELFSUP_MAX_ITEMS; ++i)
-    DSM_REQUIRE(items[i].grad_disp && items[i].grad_other, DSM_ERR_ARG);
+    DSM_REQUIRE(items[i].grad_disp && (items[i].grad_other || gather_only), DSM_ERR_ARG);
   Work W;
-  const int rc = make_work(items, n_items, flag_mask, (void*)workspace, W);
+  const int rc = make_work(items, n_items, flags, (void*)workspace, W);
   if (rc != DSM_OK) return rc;
   dsm_clear_stale_error();
-  hipLaunchKernelGGL(selfsup_bwd_tiles, dim3(W.tile0[W.n]), dim3(256), 0, (hipStream_t)stream, W,
-                     (const float*)aux, (const float*)grad_loss);
+  with_objective(flags, [&](auto o) {
+    using O = decltype(o);
+    hipLaunchKernelGGL((selfsup_bwd_tiles<O::cap, O::mask, O::ds, O::lr>), dim3(W.tile0[W.n]), dim3(256), 0,
+                       (hipStream_t)stream, W, (const float*)aux, (const float*)grad_loss);
+  });
   return dsm_launch_status();
 }

@@ -7,8 +7,13 @@
 The self-supervised ``depthmono-mask`` objective (loss.py:196-236, 393-405, 424-467; the
 preset of DSMnet_train_kitti-raw.sh) runs as ONE fused HIP op over the whole pyramid
 (``costvolume.selfsup_pyramid_loss``, csrc/selfsup.hip); ``train_step_selfsup`` /
-``validate_step_selfsup`` are stereo_selfsupervised.py:48-118 / 148-200.  ``common``,
-``SsSMnet``, ``Cap_ds_lr`` and plain ``depthmono`` (no ``-mask``) are not built.
+``validate_step_selfsup`` are stereo_selfsupervised.py:48-118 / 148-200.  The ``Cap`` objectives
+without a left-right term -- ``Cap``, ``Cap_ds``, ``Cap-mask`` and ``Cap_ds-mask``, the preset of
+DSMnet_train_kitti.sh (loss.py:238-283 ``loss_Cap_ds_lr``) -- run through the same op with its
+Cap rule: no "< 1024 valid pixels" fallback, the smoothness weight divided by 2**level of the
+output's own level, terms chosen by the name; their backward is one gather launch and
+bit-reproducible.  ``common``, ``SsSMnet``, every Cap name with ``lr`` (``Cap_ds_lr``, ...) and
+plain ``depthmono`` (no ``-mask``) are not built.
 
 The forward and backward of the model run on the HIP kernels (``costvolume`` autograd
 functions).  The supervised objective over the whole pyramid of outputs, together with the D1 /
@@ -50,10 +55,18 @@ class losses(torch.nn.Module):
             # NotImplementedError is pinned by tests/test_train.py), the fused op takes both
             self.lossfun = self.loss_depthmono
             self.lossesfun = self.losses_pyramid1
+        elif "cap" in name and "lr" not in name and "depthmono" not in name and "sssmnet" not in name:
+            # loss.py:372-374, terms by the name (:270, :275).  The names with a left-right term stay
+            # unbuilt at this level (Cap_ds_lr's NotImplementedError is pinned by
+            # tests/test_selfsup.py); the fused op takes the term
+            self.lossfun = self.loss_Cap_ds_lr
+            self.lossesfun = self.losses_pyramid1
+            self.cap_terms = ("ds",) if "ds" in name else ()
         else:
             raise NotImplementedError(
-                "loss_name=%r is not built: supervised and depthmono-mask are; common (C_ds3), "
-                "Cap_ds_lr, SsSMnet and depthmono without -mask are not" % loss_name)
+                "loss_name=%r is not built: supervised, depthmono-mask and Cap / Cap_ds / Cap-mask / "
+                "Cap_ds-mask are; common (C_ds3), SsSMnet, depthmono without -mask and every Cap name "
+                "with a left-right term (Cap_ds_lr, Cap_lr, ...) are not" % loss_name)
         self.maxepoch_weight_adjust = maxepoch_weight_adjust
         self.count_levels = count_levels
         self.weight_levels = [0] * count_levels
@@ -155,12 +168,26 @@ class losses(torch.nn.Module):
                                        [dispL1], [level], [weight], [scale_factor], self.flag_mask,
                                        [delts])
 
+    def loss_Cap_ds_lr(self, imL, imR_src, LeftTop, dispL, imL1, imR1_src, LeftTop1, dispL1,
+                       level=0, scale_factor=1, weight=1.0, delts=None, factor=1):
+        """loss.py:238-283 for ONE pyramid entry, both views, as ``loss_depthmono`` above; ``factor``
+        divides the smoothness weight (the reference passes 2**level of the output's level)."""
+        from . import costvolume as cv
+        if delts is None:
+            delts = tuple(_draw_delt() for _ in range(4))
+        return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, [dispL], imL1, imR1_src, LeftTop1,
+                                       [dispL1], [level], [weight], [scale_factor], self.flag_mask,
+                                       [delts], objective="cap", terms=self.cap_terms, ds_divisors=[factor])
+
     def losses_pyramid1(self, imR_src, imL, dispLs, scale_dispLs, LeftTop, imR1_src, imL1, dispL1s,
                         scale_dispL1s=None, LeftTop1=(0, 0)):
         """loss.py:424-467: levels above maxlevel = min(2, max level) are upsampled (stock
         autograd) to the maxlevel grid and compared with that image level; the four random
         epsilons of every weighted level are drawn in the reference's order from torch's CPU
-        generator; then ONE fused launch sequence for the whole pyramid."""
+        generator (all four, also where the objective does not use a warp: the reference draws
+        inside imwrap_BCHW, which it calls four times regardless); then ONE fused launch sequence
+        for the whole pyramid.  The Cap objectives also get 2**level of the output's OWN level
+        (loss.py:456), not the clamped one, as the divisor of their smoothness weight."""
         from . import costvolume as cv
         dispLs = [d.unsqueeze(1) if d.dim() == 3 else d for d in dispLs]      # PSMNet: (B,H,W)
         dispL1s = [d.unsqueeze(1) if d.dim() == 3 else d for d in dispL1s]
@@ -168,7 +195,7 @@ class losses(torch.nn.Module):
         h = w = None
         if maxlevel in scale_dispLs:
             _, _, h, w = dispLs[maxlevel].shape
-        ds, ds1, levels, weights, factors, delts = [], [], [], [], [], []
+        ds, ds1, levels, weights, factors, delts, divisors = [], [], [], [], [], [], []
         for i, level in enumerate(scale_dispLs):
             weight = self.weight_levels[level]
             if weight <= 0:
@@ -185,9 +212,14 @@ class losses(torch.nn.Module):
             ds1.append(dL1)
             levels.append(min(level, maxlevel))
             weights.append(weight)
+            divisors.append(2 ** level)
             delts.append(tuple(_draw_delt() for _ in range(4)))   # imL_wrap, imL1_wrap, dispL_wrap, dispL1_wrap
         if not ds:
             return 0
+        if self.lossfun == self.loss_Cap_ds_lr:
+            return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, ds, imL1, imR1_src, LeftTop1, ds1,
+                                           levels, weights, factors, self.flag_mask, delts, objective="cap",
+                                           terms=self.cap_terms, ds_divisors=divisors)
         return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, ds, imL1, imR1_src, LeftTop1, ds1,
                                        levels, weights, factors, self.flag_mask, delts)
 

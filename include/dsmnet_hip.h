@@ -586,8 +586,23 @@ int dsm_stage_images_nhwc16(const void* left, const void* right, void* out, int 
  *   dsm_selfsup_bwd   1 launch: ACCUMULATES d loss / d disp into grad_disp and grad_other of
  *                     every item (fp32 global atomics: the left-right terms scatter into the
  *                     other view's disparity); the caller zeroes them.  grad_loss: device scalar.
- * flag_mask: the "-mask" weights (weight_common).  n_items even, 2..DSM_SELFSUP_MAX_ITEMS. */
+ * flags: 0 or DSM_SELFSUP_MASK (the "-mask" weights, weight_common) = depthmono, as ever.
+ * n_items even, 2..DSM_SELFSUP_MAX_ITEMS.
+ *
+ * The "Cap[_ds][_lr][-mask]" objective (loss_Cap_ds_lr, loss.py:238-283) on the same entry points:
+ * flags = DSM_SELFSUP_CAP | [DSM_SELFSUP_MASK] | [DSM_SELFSUP_DS] | [DSM_SELFSUP_LR].  Its rule:
+ * simlary is the mean SSIM over mask_ap however few pixels that is (no fallback: aux slot 1 is 0;
+ * no valid pixel at all gives w = 0.001 and an unspecified simlary slot), the smoothness term is
+ * weighted w / ds_divisor (ds_divisor 0 means 1; depthmono ignores it), and the smoothness and
+ * left-right terms exist only with DS / LR.  Without LR dsm_selfsup_bwd is a pure gather that
+ * STORES every element of every item's grad_disp (no atomics, bit-reproducible, the buffers
+ * may be uninitialised; grad_other is not touched and may be NULL); without LR and MASK disp_other is never read.
+ * With LR it accumulates as above.  Any other flags word is DSM_ERR_ARG. */
 #define DSM_SELFSUP_MAX_ITEMS 16
+#define DSM_SELFSUP_MASK 1
+#define DSM_SELFSUP_CAP 2
+#define DSM_SELFSUP_DS 4
+#define DSM_SELFSUP_LR 8
 typedef struct dsm_selfsup_item {
   const void* im;
   const void* src;
@@ -600,13 +615,13 @@ typedef struct dsm_selfsup_item {
   int B, h, w, H0, W0;
   int left, top, scale_factor;
   float delt_im, delt_disp, weight;
-  int pad_;
+  int ds_divisor; /* Cap: C_ds is weighted w / ds_divisor; 0 = 1 (was padding) */
 } dsm_selfsup_item;
 
 size_t dsm_selfsup_workspace_floats(const dsm_selfsup_item* items, int n_items);
-int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flag_mask, void* workspace,
+int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flags, void* workspace,
                     void* loss, void* aux, dsm_stream_t stream);
-int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flag_mask, const void* workspace,
+int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flags, const void* workspace,
                     const void* aux, const void* grad_loss, dsm_stream_t stream);
 
 /* (ABI v7, additive) Supervised pyramid loss with the D1 / EPE metrics, fused (csrc/suploss.hip) --

@@ -3,7 +3,10 @@
 fused (csrc/selfsup.hip) versus the stock float32 restatement on the GPU (median of event-timed
 reps after warm-up), and the whole train_step_selfsup.  Prints one JSON line.
 
-    python scripts/bench_selfsup.py [--reps 20] [--warmup 5] [--skip-train]
+    python scripts/bench_selfsup.py [--reps 20] [--warmup 5] [--skip-train] [--loss-name NAME]
+
+``--loss-name Cap_ds-mask`` (or any other built Cap name) times the Cap objective of the same
+kernels against its restatement (tests/cap_oracle.py): the preset of DSMnet_train_kitti.sh.
 """
 import argparse
 import json
@@ -17,6 +20,7 @@ sys.path.insert(0, ROOT)
 
 from dsmnet_amd import train                    # noqa: E402
 from dsmnet_amd.models import model_create_by_name   # noqa: E402
+from tests import cap_oracle as CO              # noqa: E402
 from tests import selfsup_oracle as SO          # noqa: E402
 
 
@@ -41,6 +45,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-train", action="store_true")
+    ap.add_argument("--loss-name", default="depthmono-mask")
     args = ap.parse_args()
     B, H, W, nedge = 4, 384, 768, 64
     h, w = H - 2 * nedge, W - 2 * nedge
@@ -49,7 +54,7 @@ def main():
     batch1 = torch.flip(batch, dims=[-1])
     dLs = [(torch.rand(B, 1, h >> k, w >> k, generator=g) * 40 / 2 ** k).cuda().requires_grad_() for k in range(7)]
     dL1s = [(torch.rand(B, 1, h >> k, w >> k, generator=g) * 40 / 2 ** k).cuda().requires_grad_() for k in range(7)]
-    lossfun = train.losses("depthmono-mask", 7, 10)
+    lossfun = train.losses(args.loss_name, 7, 10)
     lossfun.Weight_Adjust_levels(3)                 # every level weighted (0.01 or more)
     a = {"imR_src": batch[:, 3:6], "imL": batch[:, :3, nedge:H - nedge, nedge:W - nedge], "dispLs": dLs,
          "scale_dispLs": list(range(7)), "LeftTop": [nedge, nedge], "imR1_src": batch1[:, :3],
@@ -60,12 +65,16 @@ def main():
         lossfun(a).backward()
 
     def stock():
-        loss, _ = SO.losses_pyramid1(lossfun.weight_levels, True, a["imR_src"], a["imL"], dLs, a["scale_dispLs"],
-                                     a["LeftTop"], a["imR1_src"], a["imL1"], dL1s, a["LeftTop1"],
-                                     dtype=torch.float32)
+        rest = (a["imR_src"], a["imL"], dLs, a["scale_dispLs"], a["LeftTop"], a["imR1_src"], a["imL1"], dL1s,
+                a["LeftTop1"])
+        if "depthmono" in args.loss_name:
+            loss, _ = SO.losses_pyramid1(lossfun.weight_levels, lossfun.flag_mask, *rest, dtype=torch.float32)
+        else:
+            loss, _ = CO.losses_pyramid1(lossfun.weight_levels, lossfun.flag_mask, CO.terms_of(args.loss_name),
+                                         *rest, dtype=torch.float32)
         loss.backward()
 
-    out = {"shape": [B, H, W], "nedge": nedge, "levels": 7, "reps": args.reps,
+    out = {"loss_name": args.loss_name, "shape": [B, H, W], "nedge": nedge, "levels": 7, "reps": args.reps,
            "loss_fwd_bwd_ms": {"fused": timed(fused, args.reps, args.warmup),
                                "stock_fp32": timed(stock, args.reps, args.warmup)}}
     out["loss_fwd_bwd_ms"]["speedup"] = out["loss_fwd_bwd_ms"]["stock_fp32"] / out["loss_fwd_bwd_ms"]["fused"]
