@@ -83,6 +83,17 @@ class SuplossItem(ctypes.Structure):
 DSM_SUPLOSS_MAX_ITEMS = 16
 
 
+class MetricsArgs(ctypes.Structure):
+    """struct dsm_metrics_args (include/dsmnet_hip.h), 72 bytes."""
+    _fields_ = [("pred", c_void_p), ("gt", c_void_p), ("imL", c_void_p), ("imR", c_void_p),
+                ("workspace", c_void_p), ("out", c_void_p), ("B", c_int), ("C", c_int), ("H", c_int),
+                ("W", c_int), ("delt", ctypes.c_float), ("flags", c_int)]
+
+
+DSM_METRICS_SLOTS = 16
+DSM_METRICS_NEGATE_WARP = 1
+
+
 class ColorRecord(ctypes.Structure):
     """struct dsm_color_record (include/dsmnet_hip.h)."""
     _fields_ = [("order", c_int * 4), ("jitter", ctypes.c_float * 4), ("flags", c_int), ("alpha_row", c_int)]
@@ -154,6 +165,8 @@ SIGNATURES = {
     "dsm_suploss_workspace_floats": (c_size_t, [c_int] * 5),
     "dsm_suploss_fwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4),
     "dsm_suploss_bwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
+    "dsm_stereo_metrics_workspace_bytes": (c_size_t, [c_int] * 3),
+    "dsm_stereo_metrics": (c_int, [ctypes.POINTER(MetricsArgs), c_void_p]),
     "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),
     "dsm_stereo_spatial": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SpatialRecord)] + [c_int] * 8 + [c_void_p]),
     "dsm_concat_conv_fwd": (c_int, [c_void_p] * 5 + [c_size_t] + [c_void_p] * 2 + [c_int] * 9 + [c_void_p]),

@@ -14,6 +14,7 @@ Reference code each op replaces (sunshinnnn/DSMnet):
                   models/util_conv.py:150-179, models/util_fun.py:41-50
   stereo_color    myTransforms/aug_color.py:28-45, 66-101, 103-203, myTransforms/__init__.py:109-135
   supervised_pyramid_loss   losses/loss.py:326-338, 407-421, stereo.py:103-113
+  stereo_metrics  utils/evaluate.py:9-73, stereo.py:103-113, utils/imwrap.py:37-72
 """
 import ctypes
 import functools
@@ -2072,3 +2073,106 @@ def stereo_spatial(x, records, out_hw, to_tensor_channels=6):
                                             int(to_tensor_channels), _stream())
     _lib.check(rc, "dsm_stereo_spatial")
     return y
+
+
+# ----------------------------------------------------------------------------
+# Evaluation metrics: D1 / EPE, the KITTI set, photometric error (csrc/metrics.hip)
+# ----------------------------------------------------------------------------
+METRIC_KEYS = ("d1", "epe", "abs_rel", "sq_rel", "rmse", "rmse_log", "d1_kitti", "a1", "a2", "a3",
+               "pixelerror", "pixelerror_elem")
+
+
+def stereo_metrics(pred, gt=None, imL=None, imR=None, delt=None, negate_warp=False):
+    """The sums behind every evaluation number of utils/evaluate.py (``evaluate``,
+    ``imwrap_pixel_errors``, ``compute_errors``) and stereo.py:103-113 ``accuracy``, in two launches
+    and without a host read (csrc/metrics.hip; the 16 slots are listed in include/dsmnet_hip.h and
+    DESIGN.md).  ``pred`` (B,1,H,W) or (B,H,W); ``gt`` (B,1,H,W) with holes <= 0, or None; ``imL`` /
+    ``imR`` (B,C,H,W), both or neither, warped as ``imwrap_BCHW(imR, pred)`` -- ``negate_warp=True``
+    samples at ``-pred``, as evaluate.py:26,40 do.  ``delt``: the warp's epsilon (None: one draw of
+    ``train._draw_delt()``, from the CPU generator).  The ``> 0`` masks of the photometric slots mean
+    "inside the right image" only for non-negative images (raw [0,1], not normalised ones).
+
+    Returns the (B,16) float64 device tensor of per-image sums; ``stereo_metrics_finish`` turns it
+    into the metrics.  The rows are additive: summing them over images, batches or ranks and then
+    finishing gives the metrics of the union.  Capturable: torch allocates, nothing synchronises."""
+    _require_device("stereo_metrics", pred, gt, imL, imR)
+    if pred.dim() == 3:
+        pred = pred.unsqueeze(1)
+    if pred.dim() != 4 or pred.shape[1] != 1 or pred.numel() == 0:
+        raise ValueError("stereo_metrics: pred must be (B,1,H,W) or (B,H,W), got %s" % (tuple(pred.shape),))
+    B, _, H, W = pred.shape
+    if gt is None and imL is None and imR is None:
+        raise ValueError("stereo_metrics: give gt, or imL and imR, or all three")
+    if (imL is None) != (imR is None):
+        raise ValueError("stereo_metrics: imL and imR come together")
+    if gt is not None and tuple(gt.shape) != (B, 1, H, W):
+        raise ValueError("stereo_metrics: gt %s does not match pred %s" % (tuple(gt.shape), tuple(pred.shape)))
+    C = 1
+    if imL is not None:
+        C = imL.shape[1] if imL.dim() == 4 else 0
+        if C < 1 or tuple(imL.shape) != (B, C, H, W) or imR.shape != imL.shape:
+            raise ValueError("stereo_metrics: imL %s and imR %s must both be (B,C,H,W) over pred %s"
+                             % (tuple(imL.shape), tuple(imR.shape), tuple(pred.shape)))
+        if min(H, W) < 2:
+            raise ValueError("stereo_metrics: maps must be larger than 1x1")        # imwrap.py:48
+        if delt is None:
+            from . import train
+            delt = train._draw_delt()
+    lib = _lib.load()
+    a = _lib.MetricsArgs()
+    keep = [t if t is None else t.contiguous() for t in (pred, gt, imL, imR)]
+    ws = torch.empty(lib.dsm_stereo_metrics_workspace_bytes(B, H, W) // 8, device=pred.device, dtype=torch.float64)
+    out = torch.empty((B, _lib.DSM_METRICS_SLOTS), device=pred.device, dtype=torch.float64)
+    a.pred, a.gt, a.imL, a.imR = [None if t is None else t.data_ptr() for t in keep]
+    a.workspace, a.out = ws.data_ptr(), out.data_ptr()
+    a.B, a.C, a.H, a.W = B, C, H, W
+    a.delt = float(delt or 0.0)
+    a.flags = _lib.DSM_METRICS_NEGATE_WARP if negate_warp else 0
+    work = 4.0 * B * H * W * (1 + (gt is not None) + (2 * C if imL is not None else 0)) + 8.0 * ws.numel()
+    with torch.cuda.device(pred.device), _timed("metrics_tiles+reduce", work):
+        rc = lib.dsm_stereo_metrics(ctypes.byref(a), _stream())
+    _lib.check(rc, "dsm_stereo_metrics")
+    out.image_shape = (C, H, W) if imL is not None else None
+    return out
+
+
+def stereo_metrics_finish(sums, per_image=False, image_shape=None):
+    """The metrics of a (B,16) tensor of ``stereo_metrics`` sums: plain torch on any device, no host
+    read.  Returns a dict of float64 tensors, 0-dim over the whole batch or (B,) with ``per_image``:
+
+        d1, epe                       evaluate / accuracy: 100 - 100 * good / n, mean |gt - pred|
+        abs_rel, sq_rel, rmse, rmse_log, d1_kitti, a1, a2, a3      compute_errors
+        pixelerror                    evaluate: 255 * mean |imL - w| over the pixels whose warped
+                                      channel sum is > 0; over every element when there is none
+        pixelerror_elem               imwrap_pixel_errors: 255 * mean over the elements with w > 0
+
+    ``image_shape`` = (C, H, W) of the images, which ``pixelerror`` needs; by default what
+    ``stereo_metrics`` noted on its result (``sums.image_shape``; sums combined from several results
+    have lost it: pass it).  Without it ``pixelerror`` is NaN.  No valid ground-truth pixel (n = 0,
+    or no gt given) makes the ground-truth metrics NaN, as numpy's empty means are; no element with
+    w > 0 makes ``pixelerror_elem`` NaN."""
+    if sums.dim() != 2 or sums.shape[1] != _lib.DSM_METRICS_SLOTS:
+        raise ValueError("stereo_metrics_finish: sums must be (B,16), got %s" % (tuple(sums.shape),))
+    if image_shape is None:
+        image_shape = getattr(sums, "image_shape", None)
+    nimg = sums.shape[0]
+    s = sums.to(torch.float64)
+    s = s if per_image else s.sum(0)
+    c = [s[..., k] for k in range(_lib.DSM_METRICS_SLOTS)]
+    n = c[0]
+    mean = s[..., :11] / n.unsqueeze(-1)                 # every ground-truth slot over n, one launch
+    pct = 100.0 * mean[..., 2:4]
+    root = torch.sqrt(mean[..., 4:6])
+    out = {"d1": 100.0 - pct[..., 0], "epe": mean[..., 1], "abs_rel": mean[..., 6], "sq_rel": mean[..., 7],
+           "rmse": root[..., 0], "rmse_log": root[..., 1], "d1_kitti": pct[..., 1],
+           "a1": mean[..., 8], "a2": mean[..., 9], "a3": mean[..., 10]}
+    if image_shape is None:
+        out["pixelerror"] = torch.full_like(n, float("nan"))
+    else:
+        C, H, W = image_shape
+        every = float((1 if per_image else nimg) * C * H * W)
+        inside = c[13] > 0
+        out["pixelerror"] = 255.0 * torch.where(inside, c[14] / (C * torch.where(inside, c[13], torch.ones_like(n))),
+                                                c[15] / every)
+    out["pixelerror_elem"] = 255.0 * c[12] / c[11]
+    return out

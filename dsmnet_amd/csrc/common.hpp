@@ -53,6 +53,49 @@ __device__ __forceinline__ float linspace_at(float start, float end, int steps, 
   return i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - i - 1);
 }
 
+// One output pixel of utils/imwrap.py:37-72 imwrap_BCHW (fliplr False, LeftTop [0,0], scale 1) as this
+// torch's grid_sample(bilinear, zeros, align_corners=False) evaluates it -- shared by warp.hip and
+// metrics.hip so that both sample the very same value.  (x, y) is the pixel of the (H, W) disparity map, d
+// its disparity, (H0, W0) the sampled image, x1 / y1 the last point of the base grid (linspace(-1, x1, W)).
+// |ix| can be huge for wild disparities: clamp before the int conversion (both taps then fall outside and
+// contribute zero, as in torch).
+struct dsm_warp_taps {
+  int x0, y0;                    // the nw tap; dereference behind i00..i11 only
+  float wx0, wx1, wy0, wy1;
+  float nw, ne, sw, se;
+  bool i00, i01, i10, i11;       // tap in bounds: nw, ne, sw, se
+};
+
+__device__ __forceinline__ dsm_warp_taps dsm_warp_taps_at(float d, int x, int y, int H, int W, int H0,
+                                                          int W0, float x1, float y1) {
+  dsm_warp_taps t;
+  const float gx = linspace_at(-1.f, x1, W, x) - d * 2.0f / (float)(W0 - 1);
+  const float gy = linspace_at(-1.f, y1, H, y);
+  const float ix = ((gx + 1.f) * (float)W0 - 1.f) / 2.f;
+  const float iy = ((gy + 1.f) * (float)H0 - 1.f) / 2.f;
+  const float fx = floorf(ix), fy = floorf(iy);
+  t.x0 = (int)fminf(fmaxf(fx, -2.f), (float)W0 + 1.f);
+  t.y0 = (int)fminf(fmaxf(fy, -2.f), (float)H0 + 1.f);
+  t.wx1 = ix - fx; t.wx0 = (fx + 1.f) - ix; t.wy1 = iy - fy; t.wy0 = (fy + 1.f) - iy;
+  const bool inx0 = t.x0 >= 0 && t.x0 < W0, inx1 = t.x0 + 1 >= 0 && t.x0 + 1 < W0;
+  const bool iny0 = t.y0 >= 0 && t.y0 < H0, iny1 = t.y0 + 1 >= 0 && t.y0 + 1 < H0;
+  t.i00 = iny0 && inx0; t.i01 = iny0 && inx1; t.i10 = iny1 && inx0; t.i11 = iny1 && inx1;
+  t.nw = t.wx0 * t.wy0; t.ne = t.wx1 * t.wy0; t.sw = t.wx0 * t.wy1; t.se = t.wx1 * t.wy1;
+  return t;
+}
+
+// the sample itself: taps in the order nw, ne, sw, se, the reference's `+ delt` on in-bounds taps only
+// (out-of-bounds taps of `im_src + delt` are zeros)
+__device__ __forceinline__ float dsm_warp_sample(const dsm_warp_taps& t, float v00, float v01, float v10,
+                                                 float v11, float delt) {
+  float v = 0.f;
+  if (t.i00) v += (v00 + delt) * t.nw;
+  if (t.i01) v += (v01 + delt) * t.ne;
+  if (t.i10) v += (v10 + delt) * t.sw;
+  if (t.i11) v += (v11 + delt) * t.se;
+  return v;
+}
+
 // sum over the wave's 64 lanes, in every lane (xor butterfly)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -25,40 +25,25 @@ __global__ __launch_bounds__(256) void warp_abs_error_kernel(
   const int y = blockIdx.y, b = blockIdx.z / ncg, c0 = (blockIdx.z % ncg) * 8;
   if (x >= W) return;
   const float d = disp[((long)b * H + y) * W + x];
-  const float gx = linspace_at(-1.f, x1, W, x) - d * 2.0f / (float)(W0 - 1);
-  const float gy = linspace_at(-1.f, y1, H, y);
-  const float ix = ((gx + 1.f) * (float)W0 - 1.f) / 2.f;
-  const float iy = ((gy + 1.f) * (float)H0 - 1.f) / 2.f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  // |ix| can be huge for wild disparities: clamp before the int conversion (both taps then
-  // fall outside and contribute zero, as in torch)
-  const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W0 + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H0 + 1.f);
-  const float wx1 = ix - fx, wx0 = (fx + 1.f) - ix, wy1 = iy - fy, wy0 = (fy + 1.f) - iy;
-  const bool inx0 = x0 >= 0 && x0 < W0, inx1 = x0 + 1 >= 0 && x0 + 1 < W0;
-  const bool iny0 = y0 >= 0 && y0 < H0, iny1 = y0 + 1 >= 0 && y0 + 1 < H0;
-  const float nw = wx0 * wy0, ne = wx1 * wy0, sw = wx0 * wy1, se = wx1 * wy1;
+  const dsm_warp_taps T = dsm_warp_taps_at(d, x, y, H, W, H0, W0, x1, y1);
   const long plane0 = (long)H0 * W0, plane = (long)H * W;
-  const float* r = R + ((long)b * C + c0) * plane0 + (long)y0 * W0 + x0;
+  const float* r = R + ((long)b * C + c0) * plane0 + (long)T.y0 * W0 + T.x0;
   const long o = ((long)b * C + c0) * plane + (long)y * W + x;
   const int nc = min(8, C - c0);
   float t[8][4], lv[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) {                  // every load of the group issued before the first use
     const float* rc = r + (c < nc ? c : 0) * plane0;
-    t[c][0] = (iny0 && inx0) ? rc[0] : 0.f;
-    t[c][1] = (iny0 && inx1) ? rc[1] : 0.f;
-    t[c][2] = (iny1 && inx0) ? rc[W0] : 0.f;
-    t[c][3] = (iny1 && inx1) ? rc[W0 + 1] : 0.f;
+    t[c][0] = T.i00 ? rc[0] : 0.f;
+    t[c][1] = T.i01 ? rc[1] : 0.f;
+    t[c][2] = T.i10 ? rc[W0] : 0.f;
+    t[c][3] = T.i11 ? rc[W0 + 1] : 0.f;
     lv[c] = L ? L[o + (c < nc ? c : 0) * plane] : 0.f;
   }
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     if (c >= nc) break;
-    float v = 0.f;                               // the same sum order as the r01 form (bit-identical)
-    if (iny0 && inx0) v += (t[c][0] + delt) * nw;
-    if (iny0 && inx1) v += (t[c][1] + delt) * ne;
-    if (iny1 && inx0) v += (t[c][2] + delt) * sw;
-    if (iny1 && inx1) v += (t[c][3] + delt) * se;
+    const float v = dsm_warp_sample(T, t[c][0], t[c][1], t[c][2], t[c][3], delt);   // the r01 form's sum order
     out[o + c * plane] = L ? fabsf(lv[c] - v) : v;
   }
 }
@@ -85,17 +70,10 @@ __global__ __launch_bounds__(256) void warp_abs_error_bwd_kernel(
   const bool valid = x < W;
   const int xc = valid ? x : W - 1;
   const float d = disp[((long)b * H + y) * W + xc];
-  const float gx = linspace_at(-1.f, x1, W, xc) - d * 2.0f / (float)(W0 - 1);
-  const float gy = linspace_at(-1.f, y1, H, y);
-  const float ix = ((gx + 1.f) * (float)W0 - 1.f) / 2.f;
-  const float iy = ((gy + 1.f) * (float)H0 - 1.f) / 2.f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W0 + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H0 + 1.f);
-  const float wx1 = ix - fx, wx0 = (fx + 1.f) - ix, wy1 = iy - fy, wy0 = (fy + 1.f) - iy;
-  const bool inx0 = valid && x0 >= 0 && x0 < W0, inx1 = valid && x0 + 1 >= 0 && x0 + 1 < W0;
-  const bool iny0 = y0 >= 0 && y0 < H0, iny1 = y0 + 1 >= 0 && y0 + 1 < H0;
-  const bool i00 = iny0 && inx0, i01 = iny0 && inx1, i10 = iny1 && inx0, i11 = iny1 && inx1;
-  const float nw = wx0 * wy0, ne = wx1 * wy0, sw = wx0 * wy1, se = wx1 * wy1;
+  const dsm_warp_taps T = dsm_warp_taps_at(d, xc, y, H, W, H0, W0, x1, y1);
+  const int x0 = T.x0, y0 = T.y0;
+  const float wy0 = T.wy0, wy1 = T.wy1, nw = T.nw, ne = T.ne, sw = T.sw, se = T.se;
+  const bool i00 = valid && T.i00, i01 = valid && T.i01, i10 = valid && T.i10, i11 = valid && T.i11;
   const long plane0 = (long)H0 * W0, plane = (long)H * W;
   float gsum = 0.f;
   for (int cg = ty; cg < ncg; cg += 4) {

@@ -127,6 +127,24 @@ def disp_predict(model, imgL_np, imgR_np, use_cuda=None):
     return d.detach().cpu().numpy()
 
 
+def evaluate_pair(imgL_np, imgR_np, disp, path_disp_gt, flip=False):
+    """(d1, epe, pixelerror) of a predicted (H,W) disparity against the ground-truth file (PFM or PNG,
+    read by ``img_rw.load_disp``; holes <= 0): ``dsmnet_amd.evaluate.evaluate`` on the raw [0,1]
+    images.  ``flip``: ``disp`` is the right view's -- the pair is mirrored and swapped back into the
+    frame it was predicted in, the ground truth with it."""
+    from .evaluate import evaluate
+    from .img_rw import load_disp
+    gt = np.asarray(load_disp(path_disp_gt), dtype=np.float32)
+    if flip:
+        imgL_np, imgR_np = np.flip(imgR_np, axis=1), np.flip(imgL_np, axis=1)
+        disp, gt = np.flip(disp, axis=-1), np.flip(gt, axis=-1)
+    if gt.shape != disp.shape:
+        raise ValueError("ground truth %s does not match the prediction %s" % (gt.shape, disp.shape))
+    chw = lambda im: np.ascontiguousarray(im, dtype=np.float32).transpose(2, 0, 1)[None] / 255.0
+    return evaluate(chw(imgL_np), chw(imgR_np), np.ascontiguousarray(disp, dtype=np.float32)[None, None],
+                    np.ascontiguousarray(gt)[None, None])
+
+
 def main(argv=None):
     from .img_rw import imread
     from .models import model_create_by_name
@@ -140,6 +158,9 @@ def main(argv=None):
     ap.add_argument("--flip", default=False, type=bool,
                     help="predict the right view's disparity (mirror both images, swap them)")
     ap.add_argument("--out", default=None, type=str, help="default dispL.png / dispR.png")
+    ap.add_argument("--path_disp_gt", default=None, type=str,
+                    help="ground-truth disparity of the predicted view (PFM or PNG): print D1, EPE and "
+                         "the photometric error (utils/evaluate.py evaluate)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("dsmnet_amd.deploy needs an MI355X: the HIP path has no CPU fallback")
@@ -152,6 +173,8 @@ def main(argv=None):
         disp, out = np.flip(disp, axis=-1), args.out or "dispR.png"
     else:
         disp, out = disp_predict(model, imgL, imgR, True), args.out or "dispL.png"
+    if args.path_disp_gt:
+        print("D1 %.4f %%  EPE %.4f px  pixelerror %.4f" % evaluate_pair(imgL, imgR, disp, args.path_disp_gt, args.flip))
     if out.endswith(".pfm"):
         from .img_rw import save_pfm
         save_pfm(out, np.ascontiguousarray(disp, dtype=np.float32))

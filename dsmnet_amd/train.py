@@ -422,3 +422,28 @@ def validate_step_selfsup(model, lossfun, batch, augment=None):
         loss, dispLs = _selfsup_forward(model, lossfun, batch, 0, augment)
     d1, epe = _selfsup_accuracy(batch, dispLs, 0)
     return float(loss), d1, epe
+
+
+def evaluate_step(model, batch, augment=None, per_image=False):
+    """Every evaluation number of one batch in two launches after the forward, without a host read:
+    ``costvolume.stereo_metrics`` on the model's first output (csrc/metrics.hip; utils/evaluate.py,
+    stereo.py:103-113).  ``batch`` (B,>=6,H,W) imL | imR [| dispL] on the device.  With >= 7 channels
+    ``batch[:, 6:7]`` is the ground truth; without, the ground-truth metrics are NaN and the
+    photometric ones are what judges a self-supervised run.  The images of the photometric error are
+    the batch's own (un-augmented, so non-negative: see ``dsmnet_amd.evaluate``), warped with the sign
+    the losses use (``imwrap_BCHW(imR, dispL)``, loss.py:449).  ``augment``: applied to the copy the
+    network sees, as in ``validate_step_selfsup`` (the reference's choice: ``transforms.Stereo_normalize()``).
+    Eval mode, no gradients, one ``amax_scope``.  Returns ``stereo_metrics_finish``'s dict of float64
+    device tensors, over the whole batch or, with ``per_image``, one value per image."""
+    from . import costvolume as cv
+    if batch.dim() != 4 or batch.shape[1] < 6:
+        raise ValueError("an evaluation batch is (B, >=6, H, W): imL | imR [| dispL]")
+    model.eval()
+    seen = batch[:, :6]
+    if augment is not None:
+        seen = augment(seen.clone())
+    with torch.no_grad(), cv.amax_scope(batch.device):
+        _, dispLs = model(seen[:, :3], seen[:, 3:6])
+        gt = batch[:, 6:7] if batch.shape[1] >= 7 else None
+        sums = cv.stereo_metrics(dispLs[0], gt, batch[:, :3], batch[:, 3:6])
+        return cv.stereo_metrics_finish(sums, per_image=per_image)

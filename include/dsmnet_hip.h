@@ -665,6 +665,44 @@ int dsm_suploss_bwd(const dsm_suploss_item* items, int n_items, const void* gt, 
                     int flag_smooth, const void* workspace, const void* aux, const void* grad_loss,
                     dsm_stream_t stream);
 
+/* (ABI v7, additive) Evaluation metrics of a disparity map, fused (csrc/metrics.hip) -- utils/evaluate.py
+ * :9-34 evaluate, :36-44 imwrap_pixel_errors, :46-73 compute_errors, stereo.py:103-113 accuracy.
+ * pred (B,1,H,W) fp32 contiguous; gt (B,1,H,W) or NULL; imL and imR (B,C,H,W), both or neither, the same
+ * H and W as pred (the warp is utils/imwrap.py:37-72 imwrap_BCHW(imR, +-pred) at LeftTop [0,0], scale 1,
+ * with the arithmetic of dsm_warp_abs_error; delt is the reference's random epsilon, drawn by the caller).
+ * Two launches (tiles, fixed-order fp64 reduction), no atomics, no host synchronisation: out (B,16) float64
+ * gets, per image, with m = gt > 0, diff = |gt - pred| and per-element arithmetic in fp32,
+ *    0 count m              1 sum diff          2 count (diff <= 3 or diff/gt <= 0.05)
+ *    3 count (diff >= 3 and diff/gt >= 0.05)     4 sum diff^2    5 sum (ln gt - ln(pred + 1e-6))^2
+ *    6 sum diff/gt          7 sum diff^2/gt      8-10 count max(gt/(pred + 1e-6), pred/gt) < 1.25, 1.25^2, 1.25^3
+ *   11 count, 12 sum |imL - w| over elements with w > 0
+ *   13 pixels whose channel sum of w is > 0, 14 sum |imL - w| over all C channels of those pixels
+ *   15 sum |imL - w| over every element
+ * Slots of an absent input (0-10 without gt, 11-15 without images) are 0.  The rows are additive over
+ * images (and over ranks).  workspace: dsm_stereo_metrics_workspace_bytes(B, H, W) bytes =
+ * B * ceil(H/16) * ceil(W/64) * 16 * 8 (0 for non-positive sizes), fully overwritten.
+ * flags: 0, or DSM_METRICS_NEGATE_WARP (the warp samples at -pred, as evaluate.py:26,40 do).
+ * DSM_ERR_ARG (nothing launched): NULL args, pred, out or workspace; imL without imR or the reverse;
+ * neither gt nor images; B, C, H or W <= 0 (C = 1 without images); H or W < 2 with images (imwrap.py:48);
+ * any other flags word.  DSM_ERR_ALIGN: a map that is not 4-byte aligned, workspace or out not 8-byte
+ * aligned.  DSM_ERR_UNSUPPORTED: 2^31 tiles or more.  sizeof(dsm_metrics_args) == 72. */
+#define DSM_METRICS_SLOTS 16
+#define DSM_METRICS_NEGATE_WARP 1
+typedef struct dsm_metrics_args {
+  const void* pred;
+  const void* gt;
+  const void* imL;
+  const void* imR;
+  void* workspace;
+  void* out;
+  int B, C, H, W;
+  float delt;
+  int flags;
+} dsm_metrics_args;
+
+size_t dsm_stereo_metrics_workspace_bytes(int B, int H, int W);
+int dsm_stereo_metrics(const dsm_metrics_args* args, dsm_stream_t stream);
+
 /* (ABI v7, additive) Stereo colour augmentation of a training batch, fused -- replaces
  * myTransforms/__init__.py:109-135 Stereo_color / Stereo_normalize applied by Stereo_color_batch,
  * i.e. myTransforms/aug_color.py ColorJitter (RandomOrder :175-203 over Brightness, Contrast,
