@@ -72,6 +72,12 @@ class SelfsupItem(ctypes.Structure):
 
 # the flags word of dsm_selfsup_fwd / dsm_selfsup_bwd (include/dsmnet_hip.h)
 DSM_SELFSUP_MASK, DSM_SELFSUP_CAP, DSM_SELFSUP_DS, DSM_SELFSUP_LR = 1, 2, 4, 8
+DSM_SELFSUP_COMMON, DSM_SELFSUP_SSSMNET = 16, 32        # dsm_selfsup_ext_* only
+
+
+class SelfsupExt(ctypes.Structure):
+    """struct dsm_selfsup_ext (include/dsmnet_hip.h): the side array of SsSMnet, one per item."""
+    _fields_ = [("warp", c_void_p), ("grad_warp", c_void_p), ("delt_im1", ctypes.c_float), ("reserved", c_int)]
 
 
 class SuplossItem(ctypes.Structure):
@@ -162,6 +168,9 @@ SIGNATURES = {
     "dsm_selfsup_workspace_floats": (c_size_t, [ctypes.POINTER(SelfsupItem), c_int]),
     "dsm_selfsup_fwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
     "dsm_selfsup_bwd": (c_int, [ctypes.POINTER(SelfsupItem), c_int, c_int] + [c_void_p] * 4),
+    "dsm_selfsup_ext_workspace_floats": (c_size_t, [ctypes.POINTER(SelfsupItem), c_int, c_int]),
+    "dsm_selfsup_ext_fwd": (c_int, [ctypes.POINTER(SelfsupItem), ctypes.POINTER(SelfsupExt), c_int, c_int] + [c_void_p] * 4),
+    "dsm_selfsup_ext_bwd": (c_int, [ctypes.POINTER(SelfsupItem), ctypes.POINTER(SelfsupExt), c_int, c_int] + [c_void_p] * 4),
     "dsm_suploss_workspace_floats": (c_size_t, [c_int] * 5),
     "dsm_suploss_fwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4),
     "dsm_suploss_bwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),

@@ -1702,7 +1702,7 @@ class DecoderCatFunction(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------
-# Self-supervised depthmono[-mask] and Cap[_ds][_lr][-mask] pyramid loss (csrc/selfsup.hip)
+# Self-supervised depthmono[-mask], Cap[_ds][_lr][-mask] and common[-mask] pyramid loss (csrc/selfsup.hip)
 # ----------------------------------------------------------------------------
 _SELFSUP_TERMS = {"ds": _lib.DSM_SELFSUP_DS, "lr": _lib.DSM_SELFSUP_LR}
 
@@ -1712,6 +1712,10 @@ def _selfsup_flags(spec):
     flags = _lib.DSM_SELFSUP_MASK if spec["flag_mask"] else 0
     if spec["objective"] == "depthmono":
         return flags, ""
+    if spec["objective"] == "common":                # dsm_selfsup_ext_* (the older entry points refuse the word)
+        return flags | _lib.DSM_SELFSUP_COMMON, "_common"
+    if spec["objective"] == "sssmnet":
+        return flags | _lib.DSM_SELFSUP_SSSMNET, "_sssmnet"
     flags |= _lib.DSM_SELFSUP_CAP
     for t in spec["terms"]:
         flags |= _SELFSUP_TERMS[t]
@@ -1753,54 +1757,94 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
                 it.H0, it.W0 = src.shape[2], src.shape[3]
                 it.left, it.top = int(lt[0]), int(lt[1])
                 it.scale_factor = int(sf)
-                it.delt_im, it.delt_disp = float(spec["delts"][p][di]), float(spec["delts"][p][dd])
+                dl = spec["delts"][p]
+                if spec["objective"] == "sssmnet":      # imL_wrap, imL1_wrap, imL_wrap1, imL1_wrap1[, dispL_wrap, dispL1_wrap]
+                    dd += 2
+                it.delt_im, it.delt_disp = float(dl[di]), float(dl[dd]) if dd < len(dl) else 0.0
                 it.weight = float(spec["weights"][p])
                 it.ds_divisor = int(spec["ds_divisors"][p])
         return items
+
+    @staticmethod
+    def _ext(spec, disps, warp, gwarp=None):
+        """SsSMnet's side array: item 2p + side owns the (B,3,h,w) slices of ``warp`` / ``gwarp`` at
+        three times the offset of its disparity in the flat gradient buffer."""
+        n = len(spec["levels"])
+        ext = (_lib.SelfsupExt * (2 * n))()
+        offs, o = [], 0
+        for d in disps:
+            offs.append(o)
+            o += 3 * d.numel()
+        for p in range(n):
+            for side in range(2):
+                e = ext[2 * p + side]
+                at = 4 * offs[side * n + p]
+                e.warp = warp.data_ptr() + at
+                e.grad_warp = None if gwarp is None else gwarp.data_ptr() + at
+                e.delt_im1 = float(spec["delts"][p][2 + side])
+        return ext
 
     @staticmethod
     def forward(ctx, spec, imL, imR_src, imL1, imR1_src, *disps):
         imgs = (imL, imR_src, imL1, imR1_src)
         items = SelfsupPyramidLossFunction._items(spec, imgs, disps)
         lib = _lib.load()
-        nf = lib.dsm_selfsup_workspace_floats(items, len(items))
+        flags, tag = _selfsup_flags(spec)
+        sss = bool(flags & _lib.DSM_SELFSUP_SSSMNET)
+        ext = sss or bool(flags & _lib.DSM_SELFSUP_COMMON)
+        nf = (lib.dsm_selfsup_ext_workspace_floats(items, len(items), flags) if ext
+              else lib.dsm_selfsup_workspace_floats(items, len(items)))
         if nf == 0:
             raise ValueError("selfsup_pyramid_loss: empty or invalid item list")
         ws = torch.empty(nf, device=imL.device, dtype=torch.float32)
         loss = torch.empty((), device=imL.device, dtype=torch.float32)
         aux = torch.empty(4 * len(items), device=imL.device, dtype=torch.float32)
-        flags, tag = _selfsup_flags(spec)
-        # both objectives enter the library once for two kernels; depthmono keeps the label under which
-        # its timings are on record, Cap's names the kernels "+"-joined, as suploss's does
-        label = "selfsup%s_fwd%s" % (tag, "_tiles+reduce" if tag else "")
-        with torch.cuda.device(imL.device), _timed(label, 4.0 * nf):
-            rc = lib.dsm_selfsup_fwd(items, len(items), flags, _p(ws), _p(loss), _p(aux), _stream())
-        _lib.check(rc, "dsm_selfsup_fwd")
+        # every objective enters the library once; depthmono keeps the label under which its timings
+        # are on record, the others name their kernels "+"-joined, as suploss's does
+        label = "selfsup%s_fwd%s" % (tag, ("_warp+tiles+reduce" if sss else "_gradmean+tiles+reduce" if ext
+                                           else "_tiles+reduce") if tag else "")
+        # SsSMnet: every item's im_wrap, written by the first launch, kept for the backward
+        warp = torch.empty(3 * sum(d.numel() for d in disps) if sss else 0, device=imL.device, dtype=torch.float32)
+        with torch.cuda.device(imL.device), _timed(label, 4.0 * (nf + warp.numel())):
+            if ext:
+                side = SelfsupPyramidLossFunction._ext(spec, disps, warp) if sss else None
+                rc = lib.dsm_selfsup_ext_fwd(items, side, len(items), flags, _p(ws), _p(loss), _p(aux), _stream())
+            else:
+                rc = lib.dsm_selfsup_fwd(items, len(items), flags, _p(ws), _p(loss), _p(aux), _stream())
+        _lib.check(rc, "dsm_selfsup_ext_fwd" if ext else "dsm_selfsup_fwd")
         ctx.spec = spec
-        ctx.save_for_backward(imL, imR_src, imL1, imR1_src, ws, aux, *disps)
+        ctx.save_for_backward(imL, imR_src, imL1, imR1_src, ws, aux, warp, *disps)
         ctx.mark_non_differentiable(aux)
         return loss, aux
 
     @staticmethod
     def backward(ctx, gloss, gaux):
         saved = ctx.saved_tensors
-        imgs, ws, aux, disps = saved[:4], saved[4], saved[5], saved[6:]
+        imgs, ws, aux, warp, disps = saved[:4], saved[4], saved[5], saved[6], saved[7:]
         flags, tag = _selfsup_flags(ctx.spec)
         # with the lr term the kernel accumulates (the other view scatters in); without it every
         # element is stored by its one writer, so the buffer needs no fill launch
         scatter = not (flags & _lib.DSM_SELFSUP_CAP) or bool(flags & _lib.DSM_SELFSUP_LR)
-        flat = (torch.zeros if scatter else torch.empty)(sum(d.numel() for d in disps), device=ws.device,
-                                                         dtype=torch.float32)
+        sss = bool(flags & _lib.DSM_SELFSUP_SSSMNET)
+        nd = sum(d.numel() for d in disps)
+        # SsSMnet: the scatter goes into a zeroed (B,3,h,w) buffer per item, which shares the one fill
+        # with the gradient buffer
+        flat = (torch.zeros if scatter else torch.empty)(nd + warp.numel(), device=ws.device, dtype=torch.float32)
         grads, o = [], 0
         for d in disps:
             grads.append(flat[o:o + d.numel()].view(d.shape))
             o += d.numel()
         items = SelfsupPyramidLossFunction._items(ctx.spec, imgs, disps, grads)
         g = gloss.to(torch.float32).contiguous()
-        label = "selfsup%s_bwd%s" % (tag, "" if scatter else "_gather")
+        label = "selfsup%s_bwd%s" % (tag, "_tiles+chain" if sss else "" if scatter else "_gather")
+        ext = sss or bool(flags & _lib.DSM_SELFSUP_COMMON)
         with torch.cuda.device(ws.device), _timed(label, 4.0 * (ws.numel() + 2 * flat.numel())):
-            rc = _lib.load().dsm_selfsup_bwd(items, len(items), flags, _p(ws), _p(aux), _p(g), _stream())
-        _lib.check(rc, "dsm_selfsup_bwd")
+            if ext:
+                side = SelfsupPyramidLossFunction._ext(ctx.spec, disps, warp, flat[nd:]) if sss else None
+                rc = _lib.load().dsm_selfsup_ext_bwd(items, side, len(items), flags, _p(ws), _p(aux), _p(g), _stream())
+            else:
+                rc = _lib.load().dsm_selfsup_bwd(items, len(items), flags, _p(ws), _p(aux), _p(g), _stream())
+        _lib.check(rc, "dsm_selfsup_ext_bwd" if ext else "dsm_selfsup_bwd")
         return (None, None, None, None, None) + tuple(grads)
 
 
@@ -1827,15 +1871,37 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
     integers; None: 1).  The forward is the same two launches.  Without "lr" the backward is ONE
     gather launch into an unfilled buffer and the gradient is bit-reproducible; with it, the fill
     and the scatter of depthmono.  depthmono always has
-    both terms and no divisor: ``terms`` and ``ds_divisors`` must be left at their defaults."""
+    both terms and no divisor: ``terms`` and ``ds_divisors`` must be left at their defaults.
+
+    ``objective="common"``: loss_common (loss.py:154-194) -- depthmono's rule in everything (the
+    fallback, both terms, the masks, w_ds = w_lr = w, four epsilons) with the depth-ratio
+    smoothness C_ds3 (loss.py:99-114) in place of C_ds1: on d = |disp| + 1,
+    |d[i]/d[i+1] + d[i]/d[i-1] - 2| clamped to [0, 10], weighted by
+    exp(-max_c |diff1(im)| / (0.5 m)) with m the mean of |diff1(im)| over (C,H,W) of each batch
+    sample, x and y apart.  One more forward launch sums those means in a fixed order (loss and
+    aux stay bit-identical from run to run); the backward is depthmono's fill and scatter.
+    ``terms`` and ``ds_divisors`` must be left at their defaults.
+
+    ``objective="sssmnet"``: loss_SsSMnet through losses_pyramid2 (loss.py:285-324, 469-512) -- per
+    view C_ap = mean(0.425(1-ssim) + 0.15(|im-im_wrap| + C_imdiff1(im, im_wrap))), C_lr =
+    mean|im - im_wrap1| with im_wrap1 the OTHER view's im_wrap warped again by this view's
+    disparity (fliplr), C_ds = mean C_ds2(im, disp) weighted w / ``ds_divisors[p]``, 1e-4 mean|disp|;
+    w from the mean SSIM over mask_ap with no fallback (no valid pixel: w = 0.001).  ``delts[p]``:
+    imL_wrap, imL1_wrap, imL_wrap1, imL1_wrap1 and, with ``flag_mask`` only, dispL_wrap, dispL1_wrap
+    (4 or 6 values).  Forward 3 launches (every im_wrap, tiles, reduce); backward the fill and 2: the
+    tiles scatter d C_lr / d im_wrap into the other view's zeroed buffer, a second launch chains it
+    to the disparity.  ``terms`` must be left at its default."""
     n = len(dispLs)
-    if objective not in ("depthmono", "cap"):
-        raise ValueError("selfsup_pyramid_loss: objective %r is neither 'depthmono' nor 'cap'" % (objective,))
+    if objective not in ("depthmono", "cap", "common", "sssmnet"):
+        raise ValueError("selfsup_pyramid_loss: objective %r is none of 'depthmono', 'cap', 'common', 'sssmnet'"
+                         % (objective,))
     terms = tuple(terms)
     if any(t not in _SELFSUP_TERMS for t in terms):
         raise ValueError("selfsup_pyramid_loss: terms %r: only 'ds' and 'lr' exist" % (terms,))
-    if objective == "depthmono" and (set(terms) != {"ds", "lr"} or ds_divisors is not None):
-        raise ValueError("selfsup_pyramid_loss: depthmono has both terms and no ds_divisors")
+    if objective != "cap" and set(terms) != {"ds", "lr"}:
+        raise ValueError("selfsup_pyramid_loss: %s has both terms: leave ``terms`` at its default" % objective)
+    if objective in ("depthmono", "common") and ds_divisors is not None:
+        raise ValueError("selfsup_pyramid_loss: %s has both terms and no ds_divisors" % objective)
     if ds_divisors is None:
         ds_divisors = [1] * n
     if len(ds_divisors) != n or any(int(v) != v or int(v) < 1 for v in ds_divisors):
@@ -1844,6 +1910,10 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
         raise ValueError("selfsup_pyramid_loss: one level, weight, factor and delt set per disparity")
     if 2 * n > 16:
         raise ValueError("selfsup_pyramid_loss: at most 8 pyramid entries, got %d" % n)
+    n_delts = 6 if objective == "sssmnet" and flag_mask else 4
+    if any(len(dl) != n_delts for dl in delts):
+        raise ValueError("selfsup_pyramid_loss: %s%s takes %s epsilons per entry"
+                         % (objective, "-mask" if flag_mask else "", "six" if n_delts == 6 else "four"))
     _require_device("selfsup_pyramid_loss", imL, imR_src, imL1, imR1_src, *dispLs, *dispL1s)
     dev = imL.device
     for t in (imR_src, imL1, imR1_src) + tuple(dispLs) + tuple(dispL1s):
@@ -1872,8 +1942,8 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
                                  % (p, tuple(d.shape), k, (B, 1, hk, wk)))
             if hk <= 1 or wk <= 1:
                 raise ValueError("selfsup_pyramid_loss: maps must be larger than 1x1")
-        if int(factors[p]) < 1 or len(delts[p]) != 4:
-            raise ValueError("selfsup_pyramid_loss: bad factor / delts at entry %d" % p)
+        if int(factors[p]) < 1:
+            raise ValueError("selfsup_pyramid_loss: bad factor at entry %d" % p)
     ds = [d.contiguous() for d in dispLs] + [d.contiguous() for d in dispL1s]
     spec = {"levels": [int(k) for k in levels], "factors": [int(f) for f in factors],
             "weights": [float(x) for x in weights], "delts": [tuple(float(x) for x in dl) for dl in delts],

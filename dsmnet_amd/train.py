@@ -12,8 +12,12 @@ without a left-right term -- ``Cap``, ``Cap_ds``, ``Cap-mask`` and ``Cap_ds-mask
 DSMnet_train_kitti.sh (loss.py:238-283 ``loss_Cap_ds_lr``) -- run through the same op with its
 Cap rule: no "< 1024 valid pixels" fallback, the smoothness weight divided by 2**level of the
 output's own level, terms chosen by the name; their backward is one gather launch and
-bit-reproducible.  ``common``, ``SsSMnet``, every Cap name with ``lr`` (``Cap_ds_lr``, ...) and
-plain ``depthmono`` (no ``-mask``) are not built.
+bit-reproducible.  ``losses`` refuses ``common``, ``SsSMnet``, every Cap name with ``lr``
+(``Cap_ds_lr``, ...) and plain ``depthmono`` (no ``-mask``): existing tests pin that gate.
+``selfsup_losses``, its subclass, takes them all: ``common[-mask]`` (loss.py:154-194, depthmono's
+rule with the depth-ratio smoothness C_ds3) is the op's ``objective="common"``, ``SsSMnet[-mask]``
+(loss.py:285-324 through ``losses_pyramid2``, the warp of a warp) its ``objective="sssmnet"``; the
+Cap names with ``lr`` and plain ``depthmono`` were always in the op.
 
 The forward and backward of the model run on the HIP kernels (``costvolume`` autograd
 functions).  The supervised objective over the whole pyramid of outputs, together with the D1 /
@@ -179,16 +183,12 @@ class losses(torch.nn.Module):
                                        [dispL1], [level], [weight], [scale_factor], self.flag_mask,
                                        [delts], objective="cap", terms=self.cap_terms, ds_divisors=[factor])
 
-    def losses_pyramid1(self, imR_src, imL, dispLs, scale_dispLs, LeftTop, imR1_src, imL1, dispL1s,
-                        scale_dispL1s=None, LeftTop1=(0, 0)):
-        """loss.py:424-467: levels above maxlevel = min(2, max level) are upsampled (stock
-        autograd) to the maxlevel grid and compared with that image level; the four random
+    def _pyramid_entries(self, dispLs, dispL1s, scale_dispLs, n_delts=4, skip=lambda weight: weight <= 0):
+        """The weighted entries of losses_pyramid1 / losses_pyramid2 (loss.py:426-446, 471-491) as the
+        lists the fused op takes: levels above maxlevel = min(2, max level) are upsampled (stock
+        autograd) to the maxlevel grid and compared with that image level; the ``n_delts`` random
         epsilons of every weighted level are drawn in the reference's order from torch's CPU
-        generator (all four, also where the objective does not use a warp: the reference draws
-        inside imwrap_BCHW, which it calls four times regardless); then ONE fused launch sequence
-        for the whole pyramid.  The Cap objectives also get 2**level of the output's OWN level
-        (loss.py:456), not the clamped one, as the divisor of their smoothness weight."""
-        from . import costvolume as cv
+        generator.  ``divisors``: 2**level of the output's OWN level (loss.py:456, 503)."""
         dispLs = [d.unsqueeze(1) if d.dim() == 3 else d for d in dispLs]      # PSMNet: (B,H,W)
         dispL1s = [d.unsqueeze(1) if d.dim() == 3 else d for d in dispL1s]
         maxlevel = min(2, max(scale_dispLs))
@@ -198,7 +198,7 @@ class losses(torch.nn.Module):
         ds, ds1, levels, weights, factors, delts, divisors = [], [], [], [], [], [], []
         for i, level in enumerate(scale_dispLs):
             weight = self.weight_levels[level]
-            if weight <= 0:
+            if skip(weight):
                 continue
             if level > maxlevel:
                 s = 2 ** (level - maxlevel)
@@ -213,18 +213,102 @@ class losses(torch.nn.Module):
             levels.append(min(level, maxlevel))
             weights.append(weight)
             divisors.append(2 ** level)
-            delts.append(tuple(_draw_delt() for _ in range(4)))   # imL_wrap, imL1_wrap, dispL_wrap, dispL1_wrap
+            delts.append(tuple(_draw_delt() for _ in range(n_delts)))
+        return ds, ds1, levels, weights, factors, delts, divisors
+
+    def _objective_kwargs(self, divisors):
+        """The keywords that name the objective to the fused op (none: depthmono)."""
+        if self.lossfun == self.loss_Cap_ds_lr:
+            return {"objective": "cap", "terms": self.cap_terms, "ds_divisors": divisors}
+        return {}
+
+    def losses_pyramid1(self, imR_src, imL, dispLs, scale_dispLs, LeftTop, imR1_src, imL1, dispL1s,
+                        scale_dispL1s=None, LeftTop1=(0, 0)):
+        """loss.py:424-467: the four random epsilons of every weighted level are drawn in the
+        reference's order -- imL_wrap, imL1_wrap, dispL_wrap, dispL1_wrap -- (all four, also where
+        the objective does not use a warp: the reference draws inside imwrap_BCHW, which it calls
+        four times regardless); then ONE fused launch sequence for the whole pyramid.  The Cap
+        objectives also get 2**level of the output's OWN level (loss.py:456), not the clamped one,
+        as the divisor of their smoothness weight."""
+        from . import costvolume as cv
+        ds, ds1, levels, weights, factors, delts, divisors = self._pyramid_entries(dispLs, dispL1s, scale_dispLs)
         if not ds:
             return 0
-        if self.lossfun == self.loss_Cap_ds_lr:
-            return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, ds, imL1, imR1_src, LeftTop1, ds1,
-                                           levels, weights, factors, self.flag_mask, delts, objective="cap",
-                                           terms=self.cap_terms, ds_divisors=divisors)
         return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, ds, imL1, imR1_src, LeftTop1, ds1,
-                                       levels, weights, factors, self.flag_mask, delts)
+                                       levels, weights, factors, self.flag_mask, delts,
+                                       **self._objective_kwargs(divisors))
 
     def forward(self, args):
         return self.lossesfun(**args)
+
+
+class selfsup_losses(losses):
+    """Every self-supervised name of the reference's ``losses`` (loss.py:345-348) on the fused op,
+    dispatched in ``setlossfun``'s order (:362-377): ``depthmono[-mask]``, ``SsSMnet[-mask]``, every
+    ``Cap`` name -- those with a left-right term too -- and ``common[-mask]``.  ``losses`` itself
+    keeps refusing the names it always refused (existing tests pin its gate; opening it is a
+    one-line change for whoever may edit them); for the names it builds, this class makes the same
+    calls and gives the same bits.  ``supervised`` belongs to ``losses``."""
+
+    def __init__(self, loss_name="depthmono-mask", count_levels=1, maxepoch_weight_adjust=1):
+        name = loss_name.split("-")[0].lower()
+        if not (name in ("supervised", "depthmono", "sssmnet", "cap_ds_lr", "common") or "cap" in name):
+            raise ValueError("loss_name=%r is none of the reference's (loss.py:347-348)" % loss_name)
+        if "supervised" in name:                     # setlossfun's first branch
+            raise ValueError("loss_name=%r is not self-supervised: use train.losses" % loss_name)
+        # the parent's constructor for the level weights and the bookkeeping, under a name that passes
+        # its gate; what the name selects is set below
+        super(selfsup_losses, self).__init__("depthmono-mask", count_levels, maxepoch_weight_adjust)
+        self.flag_mask = "mask" in loss_name
+        if "depthmono" in name:                      # loss.py:366-377, in that order
+            self.lossfun, self.lossesfun = self.loss_depthmono, self.losses_pyramid1
+        elif "sssmnet" in name:
+            self.lossfun, self.lossesfun = self.loss_SsSMnet, self.losses_pyramid2
+        elif "cap" in name:
+            self.lossfun, self.lossesfun = self.loss_Cap_ds_lr, self.losses_pyramid1
+            self.cap_terms = tuple(t for t in ("ds", "lr") if t in name)          # loss.py:270, 275
+        else:                                        # "common": the only name left after the check above
+            self.lossfun, self.lossesfun = self.loss_common, self.losses_pyramid1
+
+    def _objective_kwargs(self, divisors):
+        if self.lossfun == self.loss_common:
+            return {"objective": "common"}
+        return super(selfsup_losses, self)._objective_kwargs(divisors)
+
+    def loss_common(self, imL, imR_src, LeftTop, dispL, imL1, imR1_src, LeftTop1, dispL1,
+                    level=0, scale_factor=1, weight=1.0, delts=None):
+        """loss.py:154-194 for ONE pyramid entry, both views, as ``loss_depthmono``."""
+        from . import costvolume as cv
+        if delts is None:
+            delts = tuple(_draw_delt() for _ in range(4))
+        return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, [dispL], imL1, imR1_src, LeftTop1,
+                                       [dispL1], [level], [weight], [scale_factor], self.flag_mask,
+                                       [delts], objective="common")
+
+    def loss_SsSMnet(self, imL, imR_src, LeftTop, dispL, imL1, imR1_src, LeftTop1, dispL1,
+                     level=0, scale_factor=1, weight=1.0, delts=None, factor=1):
+        """loss.py:285-324 for ONE pyramid entry, both views, as ``loss_Cap_ds_lr``: ``factor``
+        divides the smoothness weight.  Four epsilons, six with ``-mask``."""
+        from . import costvolume as cv
+        if delts is None:
+            delts = tuple(_draw_delt() for _ in range(6 if self.flag_mask else 4))
+        return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, [dispL], imL1, imR1_src, LeftTop1,
+                                       [dispL1], [level], [weight], [scale_factor], self.flag_mask,
+                                       [delts], objective="sssmnet", ds_divisors=[factor])
+
+    def losses_pyramid2(self, imR_src, imL, dispLs, scale_dispLs, LeftTop, imR1_src, imL1, dispL1s,
+                        scale_dispL1s=None, LeftTop1=(0, 0)):
+        """loss.py:469-512: as ``losses_pyramid1`` with the epsilons of the reference's warps in ITS
+        order -- imL_wrap, imL1_wrap, imL_wrap1, imL1_wrap1 and, with ``-mask`` only, dispL_wrap,
+        dispL1_wrap -- and with its skip rule (a level is left out when its weight is 0, :482)."""
+        from . import costvolume as cv
+        ds, ds1, levels, weights, factors, delts, divisors = self._pyramid_entries(
+            dispLs, dispL1s, scale_dispLs, 6 if self.flag_mask else 4, lambda weight: weight == 0)
+        if not ds:
+            return 0
+        return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, ds, imL1, imR1_src, LeftTop1, ds1,
+                                       levels, weights, factors, self.flag_mask, delts,
+                                       objective="sssmnet", ds_divisors=divisors)
 
 
 def _draw_delt():

@@ -624,6 +624,40 @@ int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flags, void*
 int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flags, const void* workspace,
                     const void* aux, const void* grad_loss, dsm_stream_t stream);
 
+/* (ABI v7, additive) The objectives that the flags word above refuses, on entry points of their
+ * own (same items, same aux, same workspace contract with its own size function):
+ *   flags = DSM_SELFSUP_COMMON | [DSM_SELFSUP_MASK]   "common[-mask]" (loss_common, loss.py:154-194):
+ *     depthmono's rule -- the "< 1024 valid" fallback, both terms, w_ds = w_lr = w -- with the
+ *     depth-ratio smoothness C_ds3 (loss.py:99-114) in place of C_ds1.  Forward 3 launches (the
+ *     per-sample image-gradient sums in a fixed order, tiles, reduction), backward 1 that
+ *     ACCUMULATES as dsm_selfsup_bwd does.  ds_divisor is ignored.
+ *     ``ext`` may be NULL.
+ *   flags = DSM_SELFSUP_SSSMNET | [DSM_SELFSUP_MASK]  "SsSMnet[-mask]" (loss_SsSMnet, loss.py:285-324,
+ *     through losses_pyramid2, :469-512): C_ap with the image-gradient term C_imdiff1, C_lr =
+ *     |im - im_wrap1| with im_wrap1 the OTHER view's warped image warped again (fliplr), the
+ *     second-order smoothness C_ds2 weighted w / ds_divisor, 1e-4 mean|disp|; w from the mean SSIM
+ *     over mask_ap with no fallback (no valid pixel: w = 0.001, aux slot 1 is 0).  ``ext``: one
+ *     dsm_selfsup_ext per item -- warp (B,3,h,w) fp32, written by the forward (every item's
+ *     im_wrap) and read by the backward; grad_warp (B,3,h,w) fp32, ZEROED by the caller, backward
+ *     only; delt_im1, the epsilon of im_wrap1.  delt_disp is read with MASK only, disp_other with
+ *     MASK only, grad_other never.  Forward 3 launches (warp, tiles, reduction); backward 2: tiles,
+ *     which STORES every element of every grad_disp and scatters d loss / d im_wrap of the other
+ *     view into its grad_warp (fp32 atomics), and a chain launch that adds it to grad_disp.
+ * Any other flags word is DSM_ERR_ARG; a map with 3 h w >= 2^31 is DSM_ERR_UNSUPPORTED. */
+#define DSM_SELFSUP_COMMON 16
+#define DSM_SELFSUP_SSSMNET 32
+typedef struct dsm_selfsup_ext {
+  void* warp;
+  void* grad_warp;
+  float delt_im1;
+  int reserved;
+} dsm_selfsup_ext;
+size_t dsm_selfsup_ext_workspace_floats(const dsm_selfsup_item* items, int n_items, int flags);
+int dsm_selfsup_ext_fwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items, int flags,
+                        void* workspace, void* loss, void* aux, dsm_stream_t stream);
+int dsm_selfsup_ext_bwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items, int flags,
+                        const void* workspace, const void* aux, const void* grad_loss, dsm_stream_t stream);
+
 /* (ABI v7, additive) Supervised pyramid loss with the D1 / EPE metrics, fused (csrc/suploss.hip) --
  * losses/loss.py loss_supervised :326-338 (diff1_dx / diff1_dy :36-44), losses_pyramid0 :407-421,
  * stereo.py accuracy :103-113.  One item = one weighted output of the model: pred (B,1,hc,wc) fp32
