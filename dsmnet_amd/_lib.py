@@ -171,6 +171,8 @@ SIGNATURES = {
     "dsm_selfsup_ext_workspace_floats": (c_size_t, [ctypes.POINTER(SelfsupItem), c_int, c_int]),
     "dsm_selfsup_ext_fwd": (c_int, [ctypes.POINTER(SelfsupItem), ctypes.POINTER(SelfsupExt), c_int, c_int] + [c_void_p] * 4),
     "dsm_selfsup_ext_bwd": (c_int, [ctypes.POINTER(SelfsupItem), ctypes.POINTER(SelfsupExt), c_int, c_int] + [c_void_p] * 4),
+    "dsm_selfsup_dyn_fwd": (c_int, [ctypes.POINTER(SelfsupItem), ctypes.POINTER(SelfsupExt), c_int, c_int] + [c_void_p] * 5),
+    "dsm_selfsup_dyn_bwd": (c_int, [ctypes.POINTER(SelfsupItem), ctypes.POINTER(SelfsupExt), c_int, c_int] + [c_void_p] * 5),
     "dsm_suploss_workspace_floats": (c_size_t, [c_int] * 5),
     "dsm_suploss_fwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4),
     "dsm_suploss_bwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),

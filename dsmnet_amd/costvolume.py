@@ -1729,9 +1729,48 @@ def _int_strides(name, t):
     return st
 
 
+def _selfsup_view_scalars(dl, side, objective):
+    """(delt_im, delt_disp, delt_im1) of view ``side`` (0 left, 1 flipped) of one pyramid entry from
+    its epsilons ``dl`` in the reference's draw order: imL_wrap, imL1_wrap, dispL_wrap, dispL1_wrap
+    -- for SsSMnet imL_wrap, imL1_wrap, imL_wrap1, imL1_wrap1[, dispL_wrap, dispL1_wrap].  A
+    disparity epsilon the name does not draw is 0, as is delt_im1 outside SsSMnet.  The ONE place
+    that knows this order: the items, the side array and ``selfsup_step_params`` all ask here."""
+    sss = objective == "sssmnet"
+    dd = 2 + side + (2 if sss else 0)
+    return (float(dl[side]), float(dl[dd]) if dd < len(dl) else 0.0, float(dl[2 + side]) if sss else 0.0)
+
+
+def _selfsup_n_delts(objective, flag_mask):
+    return 6 if objective == "sssmnet" and flag_mask else 4
+
+
+def selfsup_step_params(delts, weights, objective="depthmono", flag_mask=True, out=None):
+    """The (2n, 4) float32 CPU tensor that ``selfsup_pyramid_loss(..., params=)`` reads on the device:
+    row 2p + side = [delt_im, delt_disp, delt_im1, weight] of view ``side`` of entry p
+    (include/dsmnet_hip.h, dsm_selfsup_dyn_*).  ``delts[p]``: the entry's epsilons in the reference's
+    draw order (four; six for SsSMnet with ``flag_mask``), ``weights[p]`` its level weight.  ``out``:
+    filled and returned when given (e.g. a pinned buffer)."""
+    n = len(delts)
+    if len(weights) != n or n < 1:
+        raise ValueError("selfsup_step_params: one weight per epsilon set")
+    n_delts = _selfsup_n_delts(objective, flag_mask)
+    if any(len(dl) != n_delts for dl in delts):
+        raise ValueError("selfsup_step_params: %s%s takes %d epsilons per entry"
+                         % (objective, "-mask" if flag_mask else "", n_delts))
+    rows = [_selfsup_view_scalars(delts[p], side, objective) + (float(weights[p]),)
+            for p in range(n) for side in range(2)]
+    if out is None:
+        return torch.tensor(rows, dtype=torch.float32)
+    if out.device.type != "cpu" or out.dtype != torch.float32 or tuple(out.shape) != (2 * n, 4) or not out.is_contiguous():
+        raise ValueError("selfsup_step_params: out must be a contiguous float32 CPU tensor (%d, 4)" % (2 * n))
+    out.copy_(torch.tensor(rows, dtype=torch.float32))
+    return out
+
+
 class SelfsupPyramidLossFunction(torch.autograd.Function):
     """Items 2p / 2p+1 = the two views of pyramid entry p (csrc/selfsup.hip).  ``spec`` holds the
-    host-side description; the tensors ride as arguments so that autograd sees the disparities."""
+    host-side description; the tensors ride as arguments so that autograd sees the disparities.
+    ``spec["params"]``: the device array of the per-step scalars (dsm_selfsup_dyn_*), or None."""
 
     @staticmethod
     def _items(spec, imgs, disps, grads=None):
@@ -1742,9 +1781,9 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
             k, sf = spec["levels"][p], spec["factors"][p]
             dL, dL1 = disps[p], disps[n + p]
             gL, gL1 = (grads[p], grads[n + p]) if grads is not None else (None, None)
-            for side, (im, src, lt, d, do, g, go, di, dd) in enumerate((
-                    (imL, imR_src, spec["lefttop"], dL, dL1, gL, gL1, 0, 2),
-                    (imL1, imR1_src, spec["lefttop1"], dL1, dL, gL1, gL, 1, 3))):
+            for side, (im, src, lt, d, do, g, go) in enumerate((
+                    (imL, imR_src, spec["lefttop"], dL, dL1, gL, gL1),
+                    (imL1, imR1_src, spec["lefttop1"], dL1, dL, gL1, gL))):
                 lvl = im[:, :, ::2 ** k, ::2 ** k]
                 it = items[2 * p + side]
                 it.im, it.src = lvl.data_ptr(), src.data_ptr()
@@ -1757,11 +1796,9 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
                 it.H0, it.W0 = src.shape[2], src.shape[3]
                 it.left, it.top = int(lt[0]), int(lt[1])
                 it.scale_factor = int(sf)
-                dl = spec["delts"][p]
-                if spec["objective"] == "sssmnet":      # imL_wrap, imL1_wrap, imL_wrap1, imL1_wrap1[, dispL_wrap, dispL1_wrap]
-                    dd += 2
-                it.delt_im, it.delt_disp = float(dl[di]), float(dl[dd]) if dd < len(dl) else 0.0
-                it.weight = float(spec["weights"][p])
+                if spec["params"] is None:               # else the kernels read them from the device array
+                    it.delt_im, it.delt_disp, _ = _selfsup_view_scalars(spec["delts"][p], side, spec["objective"])
+                    it.weight = float(spec["weights"][p])
                 it.ds_divisor = int(spec["ds_divisors"][p])
         return items
 
@@ -1781,7 +1818,8 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
                 at = 4 * offs[side * n + p]
                 e.warp = warp.data_ptr() + at
                 e.grad_warp = None if gwarp is None else gwarp.data_ptr() + at
-                e.delt_im1 = float(spec["delts"][p][2 + side])
+                if spec["params"] is None:
+                    e.delt_im1 = _selfsup_view_scalars(spec["delts"][p], side, spec["objective"])[2]
         return ext
 
     @staticmethod
@@ -1805,13 +1843,16 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
                                            else "_tiles+reduce") if tag else "")
         # SsSMnet: every item's im_wrap, written by the first launch, kept for the backward
         warp = torch.empty(3 * sum(d.numel() for d in disps) if sss else 0, device=imL.device, dtype=torch.float32)
+        params = spec["params"]
         with torch.cuda.device(imL.device), _timed(label, 4.0 * (nf + warp.numel())):
-            if ext:
-                side = SelfsupPyramidLossFunction._ext(spec, disps, warp) if sss else None
+            side = SelfsupPyramidLossFunction._ext(spec, disps, warp) if sss else None
+            if params is not None:
+                rc = lib.dsm_selfsup_dyn_fwd(items, side, len(items), flags, _p(params), _p(ws), _p(loss), _p(aux), _stream())
+            elif ext:
                 rc = lib.dsm_selfsup_ext_fwd(items, side, len(items), flags, _p(ws), _p(loss), _p(aux), _stream())
             else:
                 rc = lib.dsm_selfsup_fwd(items, len(items), flags, _p(ws), _p(loss), _p(aux), _stream())
-        _lib.check(rc, "dsm_selfsup_ext_fwd" if ext else "dsm_selfsup_fwd")
+        _lib.check(rc, "dsm_selfsup_dyn_fwd" if params is not None else "dsm_selfsup_ext_fwd" if ext else "dsm_selfsup_fwd")
         ctx.spec = spec
         ctx.save_for_backward(imL, imR_src, imL1, imR1_src, ws, aux, warp, *disps)
         ctx.mark_non_differentiable(aux)
@@ -1838,19 +1879,22 @@ class SelfsupPyramidLossFunction(torch.autograd.Function):
         g = gloss.to(torch.float32).contiguous()
         label = "selfsup%s_bwd%s" % (tag, "_tiles+chain" if sss else "" if scatter else "_gather")
         ext = sss or bool(flags & _lib.DSM_SELFSUP_COMMON)
+        params = ctx.spec["params"]      # kept by the spec: the array the forward read, read again now
         with torch.cuda.device(ws.device), _timed(label, 4.0 * (ws.numel() + 2 * flat.numel())):
-            if ext:
-                side = SelfsupPyramidLossFunction._ext(ctx.spec, disps, warp, flat[nd:]) if sss else None
+            side = SelfsupPyramidLossFunction._ext(ctx.spec, disps, warp, flat[nd:]) if sss else None
+            if params is not None:
+                rc = _lib.load().dsm_selfsup_dyn_bwd(items, side, len(items), flags, _p(params), _p(ws), _p(aux), _p(g), _stream())
+            elif ext:
                 rc = _lib.load().dsm_selfsup_ext_bwd(items, side, len(items), flags, _p(ws), _p(aux), _p(g), _stream())
             else:
                 rc = _lib.load().dsm_selfsup_bwd(items, len(items), flags, _p(ws), _p(aux), _p(g), _stream())
-        _lib.check(rc, "dsm_selfsup_ext_bwd" if ext else "dsm_selfsup_bwd")
+        _lib.check(rc, "dsm_selfsup_dyn_bwd" if params is not None else "dsm_selfsup_ext_bwd" if ext else "dsm_selfsup_bwd")
         return (None, None, None, None, None) + tuple(grads)
 
 
 def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1, dispL1s, levels,
                          weights, factors, flag_mask, delts, return_aux=False, objective="depthmono",
-                         terms=("ds", "lr"), ds_divisors=None):
+                         terms=("ds", "lr"), ds_divisors=None, params=None):
     """The reference's depthmono[-mask] objective over a disparity pyramid in two launches forward
     (tiles, reduce) and two backward (the gradient buffer's fill, tiles) (csrc/selfsup.hip; losses/loss.py:196-236, 393-405, 424-467,
     losses/SSIM.py, utils/imwrap.py:37-72):
@@ -1890,8 +1934,25 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
     imL_wrap, imL1_wrap, imL_wrap1, imL1_wrap1 and, with ``flag_mask`` only, dispL_wrap, dispL1_wrap
     (4 or 6 values).  Forward 3 launches (every im_wrap, tiles, reduce); backward the fill and 2: the
     tiles scatter d C_lr / d im_wrap into the other view's zeroed buffer, a second launch chains it
-    to the disparity.  ``terms`` must be left at its default."""
+    to the disparity.  ``terms`` must be left at its default.
+
+    ``params``: the per-step scalars from DEVICE memory instead of ``weights`` / ``delts`` (both must
+    then be None) -- a float32 tensor (2n, 4) on the images' device, contiguous and 16-byte aligned,
+    laid out as ``selfsup_step_params`` builds it.  The kernels read it when they run
+    (dsm_selfsup_dyn_fwd / _bwd, the same kernels), so a captured graph replays with whatever the
+    array holds at that moment; the function keeps the tensor for its backward, and its contents
+    must not change between the forward and the backward of one step.  Same values, same loss bits
+    as the host-argument form."""
     n = len(dispLs)
+    if params is not None:
+        if weights is not None or delts is not None:
+            raise ValueError("selfsup_pyramid_loss: with params, weights and delts must be None")
+        if not (torch.is_tensor(params) and params.dtype == torch.float32 and tuple(params.shape) == (2 * n, 4)
+                and params.is_contiguous() and params.device == imL.device and params.data_ptr() % 16 == 0):
+            raise ValueError("selfsup_pyramid_loss: params must be a contiguous, 16-byte aligned float32 tensor "
+                             "(%d, 4) on %s" % (2 * n, imL.device))
+    elif weights is None or delts is None:
+        raise ValueError("selfsup_pyramid_loss: weights and delts, or params")
     if objective not in ("depthmono", "cap", "common", "sssmnet"):
         raise ValueError("selfsup_pyramid_loss: objective %r is none of 'depthmono', 'cap', 'common', 'sssmnet'"
                          % (objective,))
@@ -1906,12 +1967,15 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
         ds_divisors = [1] * n
     if len(ds_divisors) != n or any(int(v) != v or int(v) < 1 for v in ds_divisors):
         raise ValueError("selfsup_pyramid_loss: ds_divisors %r: one integer >= 1 per disparity" % (ds_divisors,))
-    if not (len(dispL1s) == len(levels) == len(weights) == len(factors) == len(delts) == n) or n < 1:
+    if weights is None:
+        if not (len(dispL1s) == len(levels) == len(factors) == n) or n < 1:
+            raise ValueError("selfsup_pyramid_loss: one level and factor per disparity")
+    elif not (len(dispL1s) == len(levels) == len(weights) == len(factors) == len(delts) == n) or n < 1:
         raise ValueError("selfsup_pyramid_loss: one level, weight, factor and delt set per disparity")
     if 2 * n > 16:
         raise ValueError("selfsup_pyramid_loss: at most 8 pyramid entries, got %d" % n)
-    n_delts = 6 if objective == "sssmnet" and flag_mask else 4
-    if any(len(dl) != n_delts for dl in delts):
+    n_delts = _selfsup_n_delts(objective, flag_mask)
+    if delts is not None and any(len(dl) != n_delts for dl in delts):
         raise ValueError("selfsup_pyramid_loss: %s%s takes %s epsilons per entry"
                          % (objective, "-mask" if flag_mask else "", "six" if n_delts == 6 else "four"))
     _require_device("selfsup_pyramid_loss", imL, imR_src, imL1, imR1_src, *dispLs, *dispL1s)
@@ -1946,7 +2010,8 @@ def selfsup_pyramid_loss(imL, imR_src, lefttop, dispLs, imL1, imR1_src, lefttop1
             raise ValueError("selfsup_pyramid_loss: bad factor at entry %d" % p)
     ds = [d.contiguous() for d in dispLs] + [d.contiguous() for d in dispL1s]
     spec = {"levels": [int(k) for k in levels], "factors": [int(f) for f in factors],
-            "weights": [float(x) for x in weights], "delts": [tuple(float(x) for x in dl) for dl in delts],
+            "weights": None if weights is None else [float(x) for x in weights],
+            "delts": None if delts is None else [tuple(float(x) for x in dl) for dl in delts], "params": params,
             "lefttop": (int(lefttop[0]), int(lefttop[1])), "lefttop1": (int(lefttop1[0]), int(lefttop1[1])),
             "flag_mask": bool(flag_mask), "objective": objective, "terms": terms,
             "ds_divisors": [int(v) for v in ds_divisors]}

@@ -47,6 +47,11 @@
 // "SsSMnet[-mask]" (loss.py:285-324 loss_SsSMnet through :469-512 losses_pyramid2) has kernels of its
 // own behind the same entry points (sss_*, further down): a warp of a warp, an image-gradient term,
 // second-order smoothness and a two-stage backward.
+//
+// What changes from step to step -- the epsilons of the warps and the level weights -- reaches the
+// kernels either inside the by-value structs (read when the host launches) or, behind
+// dsm_selfsup_dyn_*, from a device array that they read when they run (Work::params, step_scalars):
+// the same kernels, so that a captured graph replays with every step's own numbers.
 #include "common.hpp"
 
 namespace {
@@ -76,7 +81,29 @@ struct Work {
   // common (C_ds3): partial sums of |diff1_dx(im)|, |diff1_dy(im)| as [item][gm_B][NCH][2]
   float* gmean;
   int gm_B;
+  // the per-step scalars as a device array [n][4] = {delt_im, delt_disp, delt_im1, weight} per item,
+  // read when the kernels run (dsm_selfsup_dyn_*: a captured graph replays with new values); NULL:
+  // the items' own fields and Warps::delt1, read at launch.  Last, so that the older offsets stay
+  const float* params;
 };
+
+// the per-step scalars of item i.  i comes from blockIdx: uniform per workgroup, one 16-byte load
+// hoisted out of the pixel loops (check_params: the array is 16-byte aligned)
+struct Step {
+  float delt_im, delt_disp, delt_im1, weight;
+};
+
+__device__ __forceinline__ Step step_scalars(const Work& W, int i, float delt_im1 = 0.f) {
+  if (W.params) {
+    const float4 v = *(const float4*)(W.params + 4 * i);
+    return Step{v.x, v.y, v.z, v.w};
+  }
+  return Step{W.it[i].delt_im, W.it[i].delt_disp, delt_im1, W.it[i].weight};
+}
+
+__device__ __forceinline__ float item_weight(const Work& W, int i) {
+  return W.params ? W.params[4 * i + 3] : W.it[i].weight;
+}
 
 __device__ __forceinline__ float sgnf(float v) { return (float)((v > 0.f) - (v < 0.f)); }
 
@@ -122,6 +149,7 @@ __device__ __forceinline__ void bil_sample(const float* p, int sy, int sx, const
 struct Pix {            // one output pixel of one item
   const dsm_selfsup_item* it;
   int i, b, y, x;
+  float delt_im, delt_disp;   // of step_scalars
 };
 
 // image warp at (y, x): im_wrap channels and their d/dix; the raw image channels too
@@ -136,7 +164,7 @@ __device__ __forceinline__ void image_warp(const Work& W, const Pix& q, float d,
                      (long)q.x * it.im_stride[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    bil_sample(src + (long)c * it.src_stride[1], it.src_stride[2], it.src_stride[3], t, it.delt_im,
+    bil_sample(src + (long)c * it.src_stride[1], it.src_stride[2], it.src_stride[3], t, q.delt_im,
                iw[c], div[c]);
     im[c] = imp[(long)c * it.im_stride[1]];
   }
@@ -149,7 +177,7 @@ __device__ __forceinline__ Bil disp_warp(const Pix& q, float d, float& dw, float
   const float gx = -(linspace_at(-1.f, 1.f, it.w, q.x) - d * 2.0f / (float)(it.w - 1));
   const float gy = linspace_at(-1.f, 1.f, it.h, q.y);
   const Bil t = bil_setup(gx, gy, it.w, it.h);
-  bil_sample((const float*)it.disp_other + (long)q.b * it.h * it.w, it.w, 1, t, it.delt_disp, dw, ddw);
+  bil_sample((const float*)it.disp_other + (long)q.b * it.h * it.w, it.w, 1, t, q.delt_disp, dw, ddw);
   return t;
 }
 
@@ -308,6 +336,7 @@ __global__ __launch_bounds__(256) void selfsup_fwd_tiles(const Work W) {
   const dsm_selfsup_item& it = W.it[i];
   int b, ty0, tx0;
   tile_origin(W, i, tile, b, ty0, tx0);
+  const Step P = step_scalars(W, i);
   const int h = it.h, w = it.w;
   const float* disp = (const float*)it.disp + (long)b * h * w;
   if (DS3 && threadIdx.x == 0) half_gradmean(W, i, b, hm[0], hm[1]);   // once per tile; read after the barrier below
@@ -318,7 +347,7 @@ __global__ __launch_bounds__(256) void selfsup_fwd_tiles(const Work W) {
     const int y = ty0 - HALO + ry, x = tx0 - HALO + rx;
     float m1 = 0.f, m2 = 0.f, q11 = 0.f, q22 = 0.f, q12 = 0.f;
     if (y >= 0 && y < h && x >= 0 && x < w) {
-      const Pix q{&it, i, b, y, x};
+      const Pix q{&it, i, b, y, x, P.delt_im, P.delt_disp};
       float iw[3], div[3], im[3];
       image_warp(W, q, disp[(long)y * w + x], iw, div, im);
       m1 = (im[0] + im[1] + im[2]) / 3.f;
@@ -338,7 +367,7 @@ __global__ __launch_bounds__(256) void selfsup_fwd_tiles(const Work W) {
   const int y = ty0 + threadIdx.x / T, x = tx0 + threadIdx.x % T;
   float part[NPART] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (y < h && x < w) {
-    const Pix q{&it, i, b, y, x};
+    const Pix q{&it, i, b, y, x, P.delt_im, P.delt_disp};
     const long o = (long)y * w + x;
     const float d = disp[o];
     float iw[3], div[3], im[3];
@@ -471,7 +500,7 @@ __global__ __launch_bounds__(256) void selfsup_reduce(const Work W, float* loss,
       aux[4 * j + 2] = (float)C[s];
       aux[4 * j + 3] = (float)simlary;
     }
-    total += (C[0] + C[1]) * (double)W.it[i].weight;
+    total += (C[0] + C[1]) * (double)item_weight(W, i);
   }
   loss[0] = (float)total;
 }
@@ -486,6 +515,7 @@ __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const flo
   const dsm_selfsup_item& it = W.it[i];
   int b, ty0, tx0;
   tile_origin(W, i, tile, b, ty0, tx0);
+  const Step P = step_scalars(W, i);
   const int h = it.h, w = it.w;
   const long n = (long)it.B * h * w;
   const float* sv = W.save + W.save0[i];
@@ -494,7 +524,7 @@ __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const flo
   const float* wim_plane = sv + (fallback ? 4 : 3) * n;
   constexpr bool unit_wim = CAP && !MASK;                     // no plane was saved: weight_im = 1
   const float wds = CAP ? wt / (float)(it.ds_divisor > 0 ? it.ds_divisor : 1) : wt;   // loss.py:272
-  const float gs = gloss[0] * it.weight;
+  const float gs = gloss[0] * P.weight;
   const float inv_n = 1.f / (float)n;
   const float* disp = (const float*)it.disp + (long)b * h * w;
   __shared__ float hm[2];               // DS3: as in the forward
@@ -518,7 +548,7 @@ __global__ __launch_bounds__(256) void selfsup_bwd_tiles(const Work W, const flo
 
   const int y = ty0 + threadIdx.x / T, x = tx0 + threadIdx.x % T;
   if (y >= h || x >= w) return;
-  const Pix q{&it, i, b, y, x};
+  const Pix q{&it, i, b, y, x, P.delt_im, P.delt_disp};
   const long o = (long)y * w + x, p = (long)b * h * w + o;
   const float d = disp[o];
   float iw[3], div[3], im[3];
@@ -614,9 +644,10 @@ __global__ __launch_bounds__(256) void sss_warp(const Work W, const Warps E) {
   const dsm_selfsup_item& it = W.it[i];
   int b, ty0, tx0;
   tile_origin(W, i, tile, b, ty0, tx0);
+  const Step P = step_scalars(W, i, E.delt1[i]);
   const int y = ty0 + threadIdx.x / T, x = tx0 + threadIdx.x % T;
   if (y >= it.h || x >= it.w) return;
-  const Pix q{&it, i, b, y, x};
+  const Pix q{&it, i, b, y, x, P.delt_im, P.delt_disp};
   const long hw = (long)it.h * it.w, o = (long)y * it.w + x;
   float iw[3], div[3], im[3];
   image_warp(W, q, ((const float*)it.disp)[b * hw + o], iw, div, im);
@@ -658,6 +689,7 @@ __global__ __launch_bounds__(256) void sss_fwd_tiles(const Work W, const Warps E
   const dsm_selfsup_item& it = W.it[i];
   int b, ty0, tx0;
   tile_origin(W, i, tile, b, ty0, tx0);
+  const Step P = step_scalars(W, i, E.delt1[i]);
   const int h = it.h, w = it.w;
   const long hw = (long)h * w;
   const float* disp = (const float*)it.disp + b * hw;
@@ -714,13 +746,13 @@ __global__ __launch_bounds__(256) void sss_fwd_tiles(const Work W, const Warps E
       if (y + 1 < h) e += fabsf((imp[(long)c * cs + ys] - im) - (wp[c * hw + o + w] - iw));
       ap += 0.15f * e;
       float v, dv;
-      bil_sample(wo + c * hw, w, 1, t, E.delt1[i], v, dv);
+      bil_sample(wo + c * hw, w, 1, t, P.delt_im1, v, dv);
       if (c == 0) iw1_0 = v;
       lr += fabsf(im - v);
     }
     float wim = 1.f, wlr = 1.f;
     if (MASK) {
-      const Pix q{&it, i, b, y, x};
+      const Pix q{&it, i, b, y, x, P.delt_im, P.delt_disp};
       float dw, ddw;
       disp_warp(q, d, dw, ddw);
       const float wc = weight_common(d, dw, it.scale_factor);
@@ -791,7 +823,7 @@ __global__ __launch_bounds__(256) void sss_reduce(const Work W, float* loss, flo
     aux[4 * j + 1] = 0.f;
     aux[4 * j + 2] = (float)c;
     aux[4 * j + 3] = (float)simlary;
-    total += c * (double)W.it[j].weight;
+    total += c * (double)item_weight(W, j);
   }
   loss[0] = (float)total;
 }
@@ -806,13 +838,14 @@ __global__ __launch_bounds__(256) void sss_bwd_tiles(const Work W, const Warps E
   const dsm_selfsup_item& it = W.it[i];
   int b, ty0, tx0;
   tile_origin(W, i, tile, b, ty0, tx0);
+  const Step P = step_scalars(W, i, E.delt1[i]);
   const int h = it.h, w = it.w;
   const long hw = (long)h * w, n = (long)it.B * hw;
   const float* sv = W.save + W.save0[i];
   const float* wimp = sv + 3 * n + b * hw;                    // weight_im of this sample (MASK only)
   const float wt = aux[4 * i + 0];
   const float wds = wt / (float)(it.ds_divisor > 0 ? it.ds_divisor : 1);
-  const float gs = gloss[0] * it.weight;
+  const float gs = gloss[0] * P.weight;
   const float inv_n = 1.f / (float)n;
   const float* disp = (const float*)it.disp + b * hw;
 
@@ -833,7 +866,7 @@ __global__ __launch_bounds__(256) void sss_bwd_tiles(const Work W, const Warps E
 
   const int y = ty0 + threadIdx.x / T, x = tx0 + threadIdx.x % T;
   if (y >= h || x >= w) return;
-  const Pix q{&it, i, b, y, x};
+  const Pix q{&it, i, b, y, x, P.delt_im, P.delt_disp};
   const long o = (long)y * w + x;
   const float d = disp[o];
   float iw[3], div[3], im[3];
@@ -850,7 +883,7 @@ __global__ __launch_bounds__(256) void sss_bwd_tiles(const Work W, const Warps E
   const float* wo = E.warp[i ^ 1] + b * 3L * hw;
   float v1[3], dv1[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) bil_sample(wo + c * hw, w, 1, t, E.delt1[i], v1[c], dv1[c]);
+  for (int c = 0; c < 3; ++c) bil_sample(wo + c * hw, w, 1, t, P.delt_im1, v1[c], dv1[c]);
   float wlr = 1.f;
   if (MASK) {
     float dw, ddw;
@@ -895,9 +928,10 @@ __global__ __launch_bounds__(256) void sss_bwd_chain(const Work W, const Warps E
   const dsm_selfsup_item& it = W.it[i];
   int b, ty0, tx0;
   tile_origin(W, i, tile, b, ty0, tx0);
+  const Step P = step_scalars(W, i, E.delt1[i]);
   const int y = ty0 + threadIdx.x / T, x = tx0 + threadIdx.x % T;
   if (y >= it.h || x >= it.w) return;
-  const Pix q{&it, i, b, y, x};
+  const Pix q{&it, i, b, y, x, P.delt_im, P.delt_disp};
   const long hw = (long)it.h * it.w, o = (long)y * it.w + x;
   float iw[3], div[3], im[3];
   image_warp(W, q, ((const float*)it.disp)[b * hw + o], iw, div, im);
@@ -949,7 +983,8 @@ int make_warps(const dsm_selfsup_ext* ext, int n, bool bwd, Warps& E) {
   return DSM_OK;
 }
 
-int make_work(const dsm_selfsup_item* items, int n, int flags, void* workspace, Work& W, bool ext = false) {
+int make_work(const dsm_selfsup_item* items, int n, int flags, void* workspace, Work& W, bool ext = false,
+              const float* params = nullptr) {
   DSM_REQUIRE(items && workspace, DSM_ERR_ARG);
   DSM_REQUIRE(n >= 2 && n <= DSM_SELFSUP_MAX_ITEMS && n % 2 == 0, DSM_ERR_ARG);
   DSM_REQUIRE(ext ? ext_objective(flags) : with_objective(flags, [](auto) {}), DSM_ERR_ARG);
@@ -1002,27 +1037,22 @@ int make_work(const dsm_selfsup_item* items, int n, int flags, void* workspace, 
   W.part = (float*)workspace;
   W.save = W.part + tiles * NPART;
   W.gmean = W.save + save;
+  W.params = params;
   return DSM_OK;
 }
 
-}  // namespace
-
-extern "C" size_t dsm_selfsup_workspace_floats(const dsm_selfsup_item* items, int n_items) {
-  if (!items || n_items < 1 || n_items > DSM_SELFSUP_MAX_ITEMS) return 0;
-  size_t f = 0;
-  for (int i = 0; i < n_items; ++i) {
-    const dsm_selfsup_item& it = items[i];
-    if (it.B <= 0 || it.h <= 0 || it.w <= 0) return 0;
-    f += (size_t)it.B * dsm_cdiv(it.w, T) * dsm_cdiv(it.h, T) * NPART + (size_t)NSAVE * it.B * it.h * it.w;
-  }
-  return f;
+// dsm_selfsup_dyn_*: the array is there and step_scalars' float4 load is aligned
+int check_params(const float* params) {
+  DSM_REQUIRE(params, DSM_ERR_ARG);
+  DSM_REQUIRE(dsm_aligned16(params), DSM_ERR_ALIGN);
+  return DSM_OK;
 }
 
-extern "C" int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flags, void* workspace,
-                               void* loss, void* aux, dsm_stream_t stream) {
+int fwd(const dsm_selfsup_item* items, int n_items, int flags, const float* params, void* workspace,
+        void* loss, void* aux, dsm_stream_t stream) {
   DSM_REQUIRE(loss && aux, DSM_ERR_ARG);
   Work W;
-  const int rc = make_work(items, n_items, flags, workspace, W);
+  const int rc = make_work(items, n_items, flags, workspace, W, false, params);
   if (rc != DSM_OK) return rc;
   dsm_clear_stale_error();
   with_objective(flags, [&](auto o) {
@@ -1035,16 +1065,15 @@ extern "C" int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int f
   return dsm_launch_status();
 }
 
-extern "C" int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flags,
-                               const void* workspace, const void* aux, const void* grad_loss,
-                               dsm_stream_t stream) {
+int bwd(const dsm_selfsup_item* items, int n_items, int flags, const float* params, const void* workspace,
+        const void* aux, const void* grad_loss, dsm_stream_t stream) {
   DSM_REQUIRE(aux && grad_loss, DSM_ERR_ARG);
   // Cap without the lr term: nothing scatters into the other view, grad_other is not needed
   const bool gather_only = (flags & DSM_SELFSUP_CAP) && !(flags & DSM_SELFSUP_LR);
   for (int i = 0; items && i < n_items && i < DSM_SELFSUP_MAX_ITEMS; ++i)
     DSM_REQUIRE(items[i].grad_disp && (items[i].grad_other || gather_only), DSM_ERR_ARG);
   Work W;
-  const int rc = make_work(items, n_items, flags, (void*)workspace, W);
+  const int rc = make_work(items, n_items, flags, (void*)workspace, W, false, params);
   if (rc != DSM_OK) return rc;
   dsm_clear_stale_error();
   with_objective(flags, [&](auto o) {
@@ -1055,22 +1084,11 @@ extern "C" int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int f
   return dsm_launch_status();
 }
 
-// ---- common[-mask] and SsSMnet[-mask]: the entry points that take the objectives
-// dsm_selfsup_fwd's flags word refuses
-
-extern "C" size_t dsm_selfsup_ext_workspace_floats(const dsm_selfsup_item* items, int n_items, int flags) {
-  const size_t f = dsm_selfsup_workspace_floats(items, n_items);
-  if (f == 0 || !ext_objective(flags)) return 0;
-  int B = 0;
-  for (int i = 0; i < n_items; ++i) B = items[i].B > B ? items[i].B : B;
-  return f + (size_t)n_items * B * NCH * 2;
-}
-
-extern "C" int dsm_selfsup_ext_fwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items,
-                                   int flags, void* workspace, void* loss, void* aux, dsm_stream_t stream) {
+int ext_fwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items, int flags,
+            const float* params, void* workspace, void* loss, void* aux, dsm_stream_t stream) {
   DSM_REQUIRE(loss && aux, DSM_ERR_ARG);
   Work W;
-  int rc = make_work(items, n_items, flags, workspace, W, true);
+  int rc = make_work(items, n_items, flags, workspace, W, true, params);
   if (rc != DSM_OK) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const dim3 tiles(W.tile0[W.n]), block(256);
@@ -1091,15 +1109,15 @@ extern "C" int dsm_selfsup_ext_fwd(const dsm_selfsup_item* items, const dsm_self
   return dsm_launch_status();
 }
 
-extern "C" int dsm_selfsup_ext_bwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items,
-                                   int flags, const void* workspace, const void* aux, const void* grad_loss,
-                                   dsm_stream_t stream) {
+int ext_bwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items, int flags,
+            const float* params, const void* workspace, const void* aux, const void* grad_loss,
+            dsm_stream_t stream) {
   DSM_REQUIRE(aux && grad_loss, DSM_ERR_ARG);
   const bool sss = (flags & DSM_SELFSUP_SSSMNET) != 0;        // SsSMnet scatters into grad_warp, not grad_other
   for (int i = 0; items && i < n_items && i < DSM_SELFSUP_MAX_ITEMS; ++i)
     DSM_REQUIRE(items[i].grad_disp && (items[i].grad_other || sss), DSM_ERR_ARG);
   Work W;
-  int rc = make_work(items, n_items, flags, (void*)workspace, W, true);
+  int rc = make_work(items, n_items, flags, (void*)workspace, W, true, params);
   if (rc != DSM_OK) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const dim3 tiles(W.tile0[W.n]), block(256);
@@ -1118,4 +1136,71 @@ extern "C" int dsm_selfsup_ext_bwd(const dsm_selfsup_item* items, const dsm_self
   hipLaunchKernelGGL((selfsup_bwd_tiles<false, false, true, true, true>), tiles, block, 0, st, W,
                      (const float*)aux, (const float*)grad_loss);
   return dsm_launch_status();
+}
+
+}  // namespace
+
+extern "C" size_t dsm_selfsup_workspace_floats(const dsm_selfsup_item* items, int n_items) {
+  if (!items || n_items < 1 || n_items > DSM_SELFSUP_MAX_ITEMS) return 0;
+  size_t f = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const dsm_selfsup_item& it = items[i];
+    if (it.B <= 0 || it.h <= 0 || it.w <= 0) return 0;
+    f += (size_t)it.B * dsm_cdiv(it.w, T) * dsm_cdiv(it.h, T) * NPART + (size_t)NSAVE * it.B * it.h * it.w;
+  }
+  return f;
+}
+
+extern "C" int dsm_selfsup_fwd(const dsm_selfsup_item* items, int n_items, int flags, void* workspace,
+                               void* loss, void* aux, dsm_stream_t stream) {
+  return fwd(items, n_items, flags, nullptr, workspace, loss, aux, stream);
+}
+
+extern "C" int dsm_selfsup_bwd(const dsm_selfsup_item* items, int n_items, int flags,
+                               const void* workspace, const void* aux, const void* grad_loss,
+                               dsm_stream_t stream) {
+  return bwd(items, n_items, flags, nullptr, workspace, aux, grad_loss, stream);
+}
+
+// ---- common[-mask] and SsSMnet[-mask]: the entry points that take the objectives
+// dsm_selfsup_fwd's flags word refuses
+
+extern "C" size_t dsm_selfsup_ext_workspace_floats(const dsm_selfsup_item* items, int n_items, int flags) {
+  const size_t f = dsm_selfsup_workspace_floats(items, n_items);
+  if (f == 0 || !ext_objective(flags)) return 0;
+  int B = 0;
+  for (int i = 0; i < n_items; ++i) B = items[i].B > B ? items[i].B : B;
+  return f + (size_t)n_items * B * NCH * 2;
+}
+
+extern "C" int dsm_selfsup_ext_fwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items,
+                                   int flags, void* workspace, void* loss, void* aux, dsm_stream_t stream) {
+  return ext_fwd(items, ext, n_items, flags, nullptr, workspace, loss, aux, stream);
+}
+
+extern "C" int dsm_selfsup_ext_bwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items,
+                                   int flags, const void* workspace, const void* aux, const void* grad_loss,
+                                   dsm_stream_t stream) {
+  return ext_bwd(items, ext, n_items, flags, nullptr, workspace, aux, grad_loss, stream);
+}
+
+// ---- the per-step scalars from device memory: every flags word of the entry points above, the same
+// kernels, `params` read when they run
+
+extern "C" int dsm_selfsup_dyn_fwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items,
+                                   int flags, const float* params, void* workspace, void* loss, void* aux,
+                                   dsm_stream_t stream) {
+  const int rc = check_params(params);
+  if (rc != DSM_OK) return rc;
+  return ext_objective(flags) ? ext_fwd(items, ext, n_items, flags, params, workspace, loss, aux, stream)
+                              : fwd(items, n_items, flags, params, workspace, loss, aux, stream);
+}
+
+extern "C" int dsm_selfsup_dyn_bwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items,
+                                   int flags, const float* params, const void* workspace, const void* aux,
+                                   const void* grad_loss, dsm_stream_t stream) {
+  const int rc = check_params(params);
+  if (rc != DSM_OK) return rc;
+  return ext_objective(flags) ? ext_bwd(items, ext, n_items, flags, params, workspace, aux, grad_loss, stream)
+                              : bwd(items, n_items, flags, params, workspace, aux, grad_loss, stream);
 }

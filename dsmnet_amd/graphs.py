@@ -88,31 +88,44 @@ class GraphedTrainStep(object):
     starts from allocations of its own (tests/test_models_gpu.py:
     ``test_graphed_train_step_after_an_eager_step_on_the_same_model``)."""
 
+    n_extra = 1          # floats after the gradients in the flat buffer: "this rank had ground truth"
+
     def __init__(self, model, optim, lossfun, example_batch, warmup=3, world=None, flat_gradients=None):
         """``flat_gradients``: force (True) the multi-rank form -- forward + backward captured, flat
         gradient exchange and optimizer step outside -- also in a single process (tests); default:
         exactly when there are several ranks."""
+        self._bind(model, optim, lossfun, world, flat_gradients)
+        if not example_batch.is_cuda or example_batch.shape[1] < 7:
+            raise ValueError("GraphedTrainStep needs a CUDA (HIP) batch (B, >=7, H, W): imL | imR | dispL")
+        lossfun.capturable = True
+        model.train()
+        self.batch = example_batch[:, :7].clone()
+        self._capture(warmup)
+
+    def _bind(self, model, optim, lossfun, world, flat_gradients):
         import torch.distributed as dist
         if world is None:
             world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.world = int(world)
         self.split = bool(flat_gradients) if flat_gradients is not None else self.world > 1
-        if not example_batch.is_cuda or example_batch.shape[1] < 7:
-            raise ValueError("GraphedTrainStep needs a CUDA (HIP) batch (B, >=7, H, W): imL | imR | dispL")
         if not all(g.get("capturable", False) for g in optim.param_groups):
-            raise ValueError("GraphedTrainStep: build the optimizer with capturable=True")
+            raise ValueError("%s: build the optimizer with capturable=True" % type(self).__name__)
         self.model, self.optim, self.lossfun = model, optim, lossfun
-        lossfun.capturable = True
-        model.train()
-        self.batch = example_batch[:, :7].clone()
+
+    def _prepare(self):
+        """Whatever ``_step`` needs that is not known before a first forward (on the warm-up stream)."""
+
+    def _capture(self, warmup):
+        """Quiesce, warm up on a side stream, quiesce again, capture ``_step`` (see the class docstring)."""
         self.flatgrads = None
         self._quiesce()
         if self.split:
             from . import sharding
-            self.flatgrads = sharding.FlatGradients(model.parameters(), n_extra=1)
+            self.flatgrads = sharding.FlatGradients(self.model.parameters(), n_extra=self.n_extra)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
+            self._prepare()
             for _ in range(warmup):
                 self._step()
         torch.cuda.current_stream().wait_stream(side)
@@ -177,6 +190,128 @@ class GraphedTrainStep(object):
         # bumped no version counter, so every fold made from these tensors is stale (DESIGN.md
         # section 9, "state that outlives a launch")
         blocks3d.invalidate_folded_caches()
+        if self.flatgrads is not None:
+            self._exchange_and_update()
+        return self.loss, self.disps
+
+
+class GraphedSelfsupStep(GraphedTrainStep):
+    """One self-supervised training step (``train.train_step_selfsup`` without its host-side metrics)
+    captured once and replayed: the two flips, both train-mode forwards inside one ``amax_scope``, the
+    fused pyramid loss, the backward and, in the single-process form, the optimizer step.
+    ``step = GraphedSelfsupStep(model, optim, lossfun, batch, augment=None, nedge=None)``;
+    ``loss, dispLs = step(next_batch)`` (static tensors; ``costvolume.stereo_metrics`` on them gives
+    D1 / EPE).  ``batch``: (B, >=6, H, W) imL | imR on the device, channels 0..5 are used.
+
+    What changes from step to step does not live in the graph.  The reference draws the epsilons of
+    its warps afresh for every step and moves the level weights every epoch; the fused loss reads
+    both from a device array when its kernels RUN (``costvolume.selfsup_pyramid_loss(params=)``,
+    dsm_selfsup_dyn_*).  A call therefore, in this order: copies the batch into its static buffer,
+    crops it and applies ``augment`` eagerly to the cropped copy (its host draws come first, as in
+    the eager step); draws the step's epsilons from the CPU generator in the reference's order
+    (``lossfun.draw_step_params``, with the current ``weight_levels``) into pinned memory and sends
+    them with a non-blocking copy -- the host never waits for the device, and a pinned buffer is
+    used again only once its copy's event has completed (else a new one is made); replays.  So
+    ``lossfun.Weight_Adjust_levels(epoch)`` between calls needs no new capture -- unless it changes
+    WHICH levels have a weight, which is the graph's shape: the call then raises ``ValueError``.
+    Build the step after the weights have been adjusted once (the constructor's default weights
+    enter the finest level only).
+
+    Several ranks, or ``flat_gradients=True``: forwards and backward are captured, into
+    ``sharding.FlatGradients`` views; ``reattach()``, one all-reduce and the optimizer step follow
+    eagerly.  Every rank draws its own augmentation and epsilons.  The rest -- capturable optimizer,
+    ``invalidate_folded_caches`` after every replay, the quiesce / warm-up / capture sequence -- is
+    ``GraphedTrainStep``'s."""
+
+    n_extra = 0          # no "had ground truth" count: every rank always has a loss
+
+    def __init__(self, model, optim, lossfun, example_batch, augment=None, nedge=None, warmup=3, world=None,
+                 flat_gradients=None):
+        self._bind(model, optim, lossfun, world, flat_gradients)
+        if not hasattr(lossfun, "draw_step_params") or lossfun.lossesfun == lossfun.losses_pyramid0:
+            raise ValueError("GraphedSelfsupStep needs a self-supervised loss (train.selfsup_losses)")
+        if not example_batch.is_cuda or example_batch.dim() != 4 or example_batch.shape[1] < 6:
+            raise ValueError("GraphedSelfsupStep needs a CUDA (HIP) batch (B, >=6, H, W): imL | imR")
+        self.nedge = nedge = (64 if lossfun.flag_mask else 0) if nedge is None else int(nedge)
+        h, w = example_batch.shape[2:]
+        if h <= 2 * nedge or w <= 2 * nedge:
+            raise ValueError("GraphedSelfsupStep: H, W must exceed 2 * nedge = %d" % (2 * nedge))
+        self.augment = augment
+        model.train()
+        self.batch = example_batch[:, :6].clone()
+        self.net_in = self._crop(self.batch).clone()          # what the network sees (augmented)
+        self.scales = self.entered = self.params = None
+        self._pinned = []                                     # [(pinned (2n,4) tensor, event of its last copy)]
+        self._capture(warmup)
+
+    def _crop(self, t):
+        n = self.nedge
+        return t[:, :, n:t.shape[2] - n, n:t.shape[3] - n]
+
+    def _prepare(self):
+        """The model's output levels are known only from a forward; with them, the levels the loss
+        enters (the captured shape) and the static device array, filled once for the warm-up."""
+        with torch.no_grad():
+            scales, _ = self.model(self.net_in[:, :3], self.net_in[:, 3:6])
+        self.scales = tuple(int(k) for k in scales)
+        self.entered = self.lossfun.entered_levels(self.scales)
+        first = self.lossfun.draw_step_params(self.scales)
+        self.params = first.to(self.batch.device)
+
+    def _send_step_params(self):
+        """This step's epsilons and weights, host to device without a host wait."""
+        slot = next((s for s in self._pinned if s[1].query()), None)
+        if slot is None:                          # every buffer may still be read by a copy in flight
+            slot = (torch.empty(tuple(self.params.shape), dtype=torch.float32, pin_memory=True), torch.cuda.Event())
+            self._pinned.append(slot)
+        self.lossfun.draw_step_params(self.scales, out=slot[0])
+        self.params.copy_(slot[0], non_blocking=True)
+        slot[1].record()
+
+    def _step_body(self):
+        b, x = self.batch, self.net_in
+        b1, x1 = torch.flip(b, dims=[-1]), torch.flip(x, dims=[-1])
+        if self.flatgrads is not None:
+            self.flatgrads.zero()
+        else:
+            self.optim.zero_grad(set_to_none=True)
+        scales, disps = self.model(x[:, :3], x[:, 3:6])
+        scales1, disps1 = self.model(x1[:, 3:6], x1[:, :3])
+        n = self.nedge
+        args = {"imR_src": b[:, 3:6], "imL": self._crop(b[:, :3]), "LeftTop": [n, n],
+                "imR1_src": b1[:, :3], "imL1": self._crop(b1[:, 3:6]), "LeftTop1": [n, n],
+                "dispLs": disps, "scale_dispLs": scales, "dispL1s": disps1, "scale_dispL1s": scales1}
+        was = self.lossfun.step_params
+        self.lossfun.step_params = self.params
+        try:
+            loss = self.lossfun(args)
+        finally:
+            self.lossfun.step_params = was
+        loss.backward()
+        if self.flatgrads is None:
+            self.optim.step()
+        return loss.detach(), [d.detach() for d in disps]
+
+    def _exchange_and_update(self):
+        self.flatgrads.reattach()
+        self.flatgrads.allreduce(self.world)
+        self.optim.step()
+
+    def __call__(self, batch):
+        if batch.shape[0] != self.batch.shape[0] or batch.shape[1] < 6 or batch.shape[2:] != self.batch.shape[2:]:
+            raise ValueError("GraphedSelfsupStep was captured for %s, got %s"
+                             % (tuple(self.batch.shape), tuple(batch.shape)))
+        entered = self.lossfun.entered_levels(self.scales)
+        if entered != self.entered:
+            raise ValueError("GraphedSelfsupStep was captured with the outputs %s entering the loss; the weights "
+                             "now enter %s: build a new step" % (list(self.entered), list(entered)))
+        from . import blocks3d
+        self.batch.copy_(batch[:, :6])
+        crop = self._crop(self.batch)
+        self.net_in.copy_(crop if self.augment is None else self.augment(crop.clone()))
+        self._send_step_params()
+        self.graph.replay()
+        blocks3d.invalidate_folded_caches()      # as in GraphedTrainStep: the replay bumped no version counter
         if self.flatgrads is not None:
             self._exchange_and_update()
         return self.loss, self.disps

@@ -19,6 +19,11 @@ rule with the depth-ratio smoothness C_ds3) is the op's ``objective="common"``, 
 (loss.py:285-324 through ``losses_pyramid2``, the warp of a warp) its ``objective="sssmnet"``; the
 Cap names with ``lr`` and plain ``depthmono`` were always in the op.
 
+A captured step (``graphs.GraphedSelfsupStep``) must not freeze what the reference changes from
+step to step: ``losses.draw_step_params`` makes a loss call's random draws ahead of it, and with
+``losses.step_params`` set the fused op reads epsilons and level weights from that device array
+when its kernels run.  ``train_step_selfsup_ranks`` is ``train_step_selfsup`` for any world size.
+
 The forward and backward of the model run on the HIP kernels (``costvolume`` autograd
 functions).  The supervised objective over the whole pyramid of outputs, together with the D1 /
 EPE of the first output, is ONE fused HIP op as well (``costvolume.supervised_pyramid_loss``,
@@ -80,6 +85,11 @@ class losses(torch.nn.Module):
         # capture of the whole step needs (graphs.GraphedTrainStep sets it)
         self.capturable = False
         self.last_metrics = None
+        # a (2n, 4) device tensor (``costvolume.selfsup_step_params``' layout, e.g. a copy of
+        # ``draw_step_params``' result): the self-supervised pyramid then draws nothing and hands the
+        # fused op this array, which its kernels read when they run -- what lets a captured step
+        # replay with every step's own epsilons and level weights (graphs.GraphedSelfsupStep)
+        self.step_params = None
 
     def Weight_Adjust_levels(self, epoch):
         """Coarse-to-fine: the unit weight slides from the coarsest output (epoch 0) to the
@@ -183,6 +193,37 @@ class losses(torch.nn.Module):
                                        [dispL1], [level], [weight], [scale_factor], self.flag_mask,
                                        [delts], objective="cap", terms=self.cap_terms, ds_divisors=[factor])
 
+    def _draw_rule(self):
+        """(objective of the fused op, epsilons per weighted level, the rule that leaves a level out)
+        of this loss: losses_pyramid1 skips ``weight <= 0`` (loss.py:436) and draws four,
+        losses_pyramid2 skips ``weight == 0`` (:482) and draws four, six with ``-mask``."""
+        if self.lossesfun == getattr(self, "losses_pyramid2", None):
+            return "sssmnet", 6 if self.flag_mask else 4, lambda weight: weight == 0
+        if self.lossesfun != self.losses_pyramid1:
+            raise ValueError("not a self-supervised loss")
+        return self._objective_kwargs(None).get("objective", "depthmono"), 4, lambda weight: weight <= 0
+
+    def entered_levels(self, scale_dispLs):
+        """Indices into ``scale_dispLs`` of the outputs the pyramid loss enters with the current
+        ``weight_levels``: a host decision, and the shape of a captured step."""
+        _, _, skip = self._draw_rule()
+        return tuple(i for i, level in enumerate(scale_dispLs) if not skip(self.weight_levels[level]))
+
+    def draw_step_params(self, scale_dispLs, out=None):
+        """The epsilons of every entered level, drawn from the CPU generator in the reference's order
+        and count -- the very calls an ordinary loss call makes -- with the current ``weight_levels``,
+        as ``costvolume.selfsup_step_params``' (2n, 4) float32 CPU tensor (``out``: filled when
+        given).  Under one seed, this followed by a loss call with ``step_params`` set uses the floats
+        an ordinary loss call would have drawn."""
+        from . import costvolume as cv
+        objective, n_delts, _ = self._draw_rule()
+        entered = self.entered_levels(scale_dispLs)
+        if not entered:
+            raise ValueError("draw_step_params: no level of %r has a weight" % (list(scale_dispLs),))
+        weights = [self.weight_levels[scale_dispLs[i]] for i in entered]
+        delts = [tuple(_draw_delt() for _ in range(n_delts)) for _ in entered]
+        return cv.selfsup_step_params(delts, weights, objective, self.flag_mask, out=out)
+
     def _pyramid_entries(self, dispLs, dispL1s, scale_dispLs, n_delts=4, skip=lambda weight: weight <= 0):
         """The weighted entries of losses_pyramid1 / losses_pyramid2 (loss.py:426-446, 471-491) as the
         lists the fused op takes: levels above maxlevel = min(2, max level) are upsampled (stock
@@ -213,8 +254,16 @@ class losses(torch.nn.Module):
             levels.append(min(level, maxlevel))
             weights.append(weight)
             divisors.append(2 ** level)
-            delts.append(tuple(_draw_delt() for _ in range(n_delts)))
+            if self.step_params is None:         # else ``draw_step_params`` drew them already
+                delts.append(tuple(_draw_delt() for _ in range(n_delts)))
+        if self.step_params is not None:        # weights and epsilons are in the device array
+            weights = delts = None
         return ds, ds1, levels, weights, factors, delts, divisors
+
+    def _step_kwargs(self):
+        """The keyword that hands the fused op the device array (none without one: the call is the
+        one it always was)."""
+        return {} if self.step_params is None else {"params": self.step_params}
 
     def _objective_kwargs(self, divisors):
         """The keywords that name the objective to the fused op (none: depthmono)."""
@@ -236,7 +285,7 @@ class losses(torch.nn.Module):
             return 0
         return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, ds, imL1, imR1_src, LeftTop1, ds1,
                                        levels, weights, factors, self.flag_mask, delts,
-                                       **self._objective_kwargs(divisors))
+                                       **self._step_kwargs(), **self._objective_kwargs(divisors))
 
     def forward(self, args):
         return self.lossesfun(**args)
@@ -308,7 +357,7 @@ class selfsup_losses(losses):
             return 0
         return cv.selfsup_pyramid_loss(imL, imR_src, LeftTop, ds, imL1, imR1_src, LeftTop1, ds1,
                                        levels, weights, factors, self.flag_mask, delts,
-                                       objective="sssmnet", ds_divisors=divisors)
+                                       objective="sssmnet", ds_divisors=divisors, **self._step_kwargs())
 
 
 def _draw_delt():
@@ -325,7 +374,10 @@ def lr_adjust(optimizer, epoch0, stride, lr0, epoch):
     n = ((epoch - epoch0) // stride) + 1
     lr = lr0 * (0.5 ** n)
     for group in optimizer.param_groups:
-        group["lr"] = lr
+        if torch.is_tensor(group["lr"]):        # a captured optimizer step reads this very tensor
+            group["lr"].fill_(lr)
+        else:
+            group["lr"] = lr
 
 
 def accuracy(dispL, dispL_gt):
@@ -354,9 +406,15 @@ class AverageMeter(object):
         self.avg = self.sum / self.count
 
 
-def make_optimizer(model, lr=1e-4, betas=(0.9, 0.999)):
-    """stereo.py:37-40 with main.py's defaults (:31-33)."""
-    return torch.optim.Adam(model.parameters(), lr=lr, betas=betas)
+def make_optimizer(model, lr=1e-4, betas=(0.9, 0.999), capturable=False):
+    """stereo.py:37-40 with main.py's defaults (:31-33).  ``capturable``: the form a captured step
+    needs (graphs.GraphedTrainStep / GraphedSelfsupStep) -- fused Adam whose learning rate is a
+    0-dim tensor on the parameters' device, which ``lr_adjust`` fills in place."""
+    if not capturable:
+        return torch.optim.Adam(model.parameters(), lr=lr, betas=betas)
+    params = list(model.parameters())
+    lr = torch.tensor(float(lr), dtype=torch.float32, device=params[0].device)
+    return torch.optim.Adam(params, lr=lr, betas=betas, capturable=True, fused=True)
 
 
 def _metrics(lossfun, disp0, disp_gt):
@@ -493,6 +551,30 @@ def train_step_selfsup(model, optim, lossfun, batch, augment=None, world=None, n
         if torch.is_tensor(loss):
             loss.backward()
             optim.step()
+    d1, epe = _selfsup_accuracy(batch, dispLs, nedge)
+    return float(loss.detach() if torch.is_tensor(loss) else loss), d1, epe
+
+
+def train_step_selfsup_ranks(model, optim, lossfun, batch, augment=None, world=None, nedge=None):
+    """``train_step_selfsup`` on any number of ranks.  One rank: exactly its calls.  Several: every
+    rank runs forward, forward, backward on its own batch -- with its own augmentation and epsilons,
+    drawn from its own generator --, then ONE flat gradient all-reduce
+    (``sharding.allreduce_gradients``: the mean over ranks) and the optimizer step.  Every rank must
+    call it every step.  Returns the rank's own (loss, D1, EPE)."""
+    from . import costvolume as cv
+    world = _world(world)
+    if world == 1:
+        return train_step_selfsup(model, optim, lossfun, batch, augment=augment, world=1, nedge=nedge)
+    if nedge is None:
+        nedge = 64 if lossfun.flag_mask else 0
+    with cv.amax_scope(batch.device):
+        model.train()
+        loss, dispLs = _selfsup_forward(model, lossfun, batch, nedge, augment)
+        optim.zero_grad()
+        if torch.is_tensor(loss):              # no weighted level: zero gradients, the collective all the same
+            loss.backward()
+        sharding.allreduce_gradients(model.parameters(), world=world)
+        optim.step()
     d1, epe = _selfsup_accuracy(batch, dispLs, nedge)
     return float(loss.detach() if torch.is_tensor(loss) else loss), d1, epe
 

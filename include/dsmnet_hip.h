@@ -658,6 +658,21 @@ int dsm_selfsup_ext_fwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ex
 int dsm_selfsup_ext_bwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items, int flags,
                         const void* workspace, const void* aux, const void* grad_loss, dsm_stream_t stream);
 
+/* (ABI v7, additive) The per-step scalars of the loss from DEVICE memory, so that a captured graph
+ * replays with each step's own epsilons and level weights.  `params` is float[n_items][4], 16-byte
+ * aligned; row i = {delt_im, delt_disp, delt_im1, weight} of item i (items ordered as above: 2p the
+ * left view of entry p, 2p + 1 the flipped one; weight of row 2p is the entry's).  The kernels
+ * read it when they RUN, one 16-byte load per workgroup; the items' delt_im / delt_disp / weight
+ * and the ext's delt_im1 are ignored.  Both take every flags word of the four entry points above
+ * (ext: SsSMnet only, else NULL) and launch the same kernels; workspace sizes as above.
+ * params NULL: DSM_ERR_ARG; not 16-byte aligned: DSM_ERR_ALIGN; every other check as above.
+ * The array must not change between a forward and its backward. */
+int dsm_selfsup_dyn_fwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items, int flags,
+                        const float* params, void* workspace, void* loss, void* aux, dsm_stream_t stream);
+int dsm_selfsup_dyn_bwd(const dsm_selfsup_item* items, const dsm_selfsup_ext* ext, int n_items, int flags,
+                        const float* params, const void* workspace, const void* aux, const void* grad_loss,
+                        dsm_stream_t stream);
+
 /* (ABI v7, additive) Supervised pyramid loss with the D1 / EPE metrics, fused (csrc/suploss.hip) --
  * losses/loss.py loss_supervised :326-338 (diff1_dx / diff1_dy :36-44), losses_pyramid0 :407-421,
  * stereo.py accuracy :103-113.  One item = one weighted output of the model: pred (B,1,hc,wc) fp32
