@@ -100,6 +100,17 @@ DSM_METRICS_SLOTS = 16
 DSM_METRICS_NEGATE_WARP = 1
 
 
+class LrcheckArgs(ctypes.Structure):
+    """struct dsm_lrcheck_args (include/dsmnet_hip.h), 80 bytes."""
+    _fields_ = [("disp", c_void_p), ("other", c_void_p), ("wrap", c_void_p), ("weight", c_void_p),
+                ("mask", c_void_p), ("masked", c_void_p), ("B", c_int), ("H", c_int), ("W", c_int),
+                ("delt", ctypes.c_float), ("factor", ctypes.c_float), ("threshold", ctypes.c_float),
+                ("flags", c_int), ("reserved", c_int)]
+
+
+DSM_LRCHECK_OTHER_RIGHT_FRAME = 1
+
+
 class ColorRecord(ctypes.Structure):
     """struct dsm_color_record (include/dsmnet_hip.h)."""
     _fields_ = [("order", c_int * 4), ("jitter", ctypes.c_float * 4), ("flags", c_int), ("alpha_row", c_int)]
@@ -178,6 +189,9 @@ SIGNATURES = {
     "dsm_suploss_bwd": (c_int, [ctypes.POINTER(SuplossItem), c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
     "dsm_stereo_metrics_workspace_bytes": (c_size_t, [c_int] * 3),
     "dsm_stereo_metrics": (c_int, [ctypes.POINTER(MetricsArgs), c_void_p]),
+    "dsm_lr_check": (c_int, [ctypes.POINTER(LrcheckArgs), c_void_p]),
+    "dsm_fill_background_workspace_bytes": (c_size_t, [c_int] * 3),
+    "dsm_fill_background": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
     "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),
     "dsm_stereo_spatial": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SpatialRecord)] + [c_int] * 8 + [c_void_p]),
     "dsm_concat_conv_fwd": (c_int, [c_void_p] * 5 + [c_size_t] + [c_void_p] * 2 + [c_int] * 9 + [c_void_p]),

@@ -15,7 +15,9 @@ Reference code each op replaces (sunshinnnn/DSMnet):
   stereo_color    myTransforms/aug_color.py:28-45, 66-101, 103-203, myTransforms/__init__.py:109-135
   supervised_pyramid_loss   losses/loss.py:326-338, 407-421, stereo.py:103-113
   stereo_metrics  utils/evaluate.py:9-73, stereo.py:103-113, utils/imwrap.py:37-72
+  lr_check        utils/imwrap.py:37-72 (fliplr=True), losses/loss.py:393-404, 451-452
 """
+import collections
 import ctypes
 import functools
 import os
@@ -2310,4 +2312,96 @@ def stereo_metrics_finish(sums, per_image=False, image_shape=None):
         out["pixelerror"] = 255.0 * torch.where(inside, c[14] / (C * torch.where(inside, c[13], torch.ones_like(n))),
                                                 c[15] / every)
     out["pixelerror_elem"] = 255.0 * c[12] / c[11]
+    return out
+
+
+# ----------------------------------------------------------------------------
+# Left-right check and background fill of a predicted map (csrc/lrcheck.hip)
+# ----------------------------------------------------------------------------
+LRCheck = collections.namedtuple("LRCheck", ("wrap", "weight", "mask", "masked"))
+
+
+def _plane_maps(name, *maps):
+    """(B,1,H,W) or (B,H,W) float32 device maps of one shape -> detached contiguous tensors, (B,H,W)."""
+    shape = tuple(maps[0].shape)
+    if len(shape) == 4 and shape[1] == 1:
+        B, H, W = shape[0], shape[2], shape[3]
+    elif len(shape) == 3:
+        B, H, W = shape
+    else:
+        raise ValueError("%s: a map is (B,1,H,W) or (B,H,W), got %s" % (name, shape))
+    for m in maps[1:]:
+        if tuple(m.shape) != shape:
+            raise ValueError("%s: shapes differ: %s vs %s" % (name, tuple(m.shape), shape))
+    if min(B, H, W) < 1:
+        raise ValueError("%s: empty map %s" % (name, shape))
+    return [m.detach().contiguous() for m in maps], (B, H, W)
+
+
+def lr_check(disp, other, mirrored=True, delt=0.0, factor=1.0, threshold=1.0,
+             want=("wrap", "weight", "mask", "masked")):
+    """Left-right consistency of ``disp`` against the other view's map, in one launch and without a
+    host read (csrc/lrcheck.hip, ``dsm_lr_check``): ``wrap = imwrap_BCHW(other, disp, fliplr=True)``
+    (utils/imwrap.py:37-72 as loss.py:451-452 call it), ``weight = weight_common(disp, wrap, factor)``
+    (loss.py:393-404), ``mask = (|disp - wrap| / factor < threshold) & (the sample lies inside the
+    image)`` as ``torch.bool`` and ``masked = disp * mask``.
+
+    ``disp`` / ``other``: (B,1,H,W) or PSMNet's (B,H,W), float32, the same shape; the results have it
+    too.  ``mirrored=True``: ``other`` was predicted from the mirrored, swapped pair and is still in
+    that frame (what the -mask objectives hand to the warp).  ``mirrored=False``: ``other`` is the
+    right camera's map in its own frame (``gcnet_LR``'s second output, what ``deploy --flip``
+    writes); it is read mirrored, without a copy, and the result is bit-identical to
+    ``lr_check(disp, other.flip(-1))``.  The right view's own check is the same call with the roles
+    swapped, in the mirrored frame.  ``delt``: the reference's warp epsilon; 0 (inference) makes the
+    result deterministic.  ``want``: the entries to compute; the others are None.
+
+    No autograd backward: the inputs are detached.  Capturable: torch allocates, nothing synchronises."""
+    _require_device("lr_check", disp, other)
+    names = tuple(want)
+    if not names or any(n not in LRCheck._fields for n in names):
+        raise ValueError("lr_check: want is a non-empty subset of %s, got %r" % (LRCheck._fields, want))
+    (d, o), (B, H, W) = _plane_maps("lr_check", disp, other)
+    if min(H, W) < 2:
+        raise ValueError("lr_check: maps must be larger than 1x1")                   # imwrap.py:48
+    out = {n: torch.empty(disp.shape, device=disp.device, dtype=torch.uint8 if n == "mask" else torch.float32)
+           for n in names}
+    a = _lib.LrcheckArgs()
+    a.disp, a.other = d.data_ptr(), o.data_ptr()
+    for n in names:
+        setattr(a, n, out[n].data_ptr())
+    a.B, a.H, a.W = B, H, W
+    a.delt, a.factor, a.threshold = float(delt), float(factor), float(threshold)
+    a.flags = 0 if mirrored else _lib.DSM_LRCHECK_OTHER_RIGHT_FRAME
+    work = B * H * W * (8.0 + sum(1.0 if n == "mask" else 4.0 for n in names))
+    with torch.cuda.device(disp.device), _timed("lr_check_tiles", work):
+        rc = _lib.load().dsm_lr_check(ctypes.byref(a), _stream())
+    _lib.check(rc, "dsm_lr_check")
+    if "mask" in out:
+        out["mask"] = out["mask"].view(torch.bool)          # the kernel writes 0 / 1
+    return LRCheck(*[out.get(n) for n in LRCheck._fields])
+
+
+def fill_background(disp, mask):
+    """``disp`` with the pixels ``mask`` rejects filled from the background, in two launches and
+    without a host read (csrc/lrcheck.hip, ``dsm_fill_background``): an invalid pixel gets the smaller
+    of the nearest valid values to its left and right in its row (the one that exists at a border),
+    a row without a valid pixel the element-wise smaller of the nearest filled rows above and below,
+    an image without a valid pixel zeros.  Valid pixels are unchanged; the value of an invalid pixel
+    is never read, so a NaN there cannot spread.  ``disp`` (B,1,H,W) or (B,H,W) float32, ``mask`` the
+    same shape, ``torch.bool`` or ``torch.uint8``.  Returns a new tensor of ``disp``'s shape.  No
+    autograd backward; capturable."""
+    _require_device("fill_background", disp)
+    if not mask.is_cuda:
+        _require_device("fill_background", mask)
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("fill_background: mask is torch.bool or torch.uint8, got %s" % (mask.dtype,))
+    if mask.shape != disp.shape:
+        raise ValueError("fill_background: mask %s does not match disp %s" % (tuple(mask.shape), tuple(disp.shape)))
+    (d, m), (B, H, W) = _plane_maps("fill_background", disp, mask)
+    lib = _lib.load()
+    out = torch.empty(disp.shape, device=disp.device, dtype=torch.float32)
+    ws = torch.empty(lib.dsm_fill_background_workspace_bytes(B, H, W) // 4, device=disp.device, dtype=torch.int32)
+    with torch.cuda.device(disp.device), _timed("fill_rows+empty_rows", 14.0 * B * H * W):
+        rc = lib.dsm_fill_background(_p(d), _p(m), _p(out), _p(ws), B, H, W, _stream())
+    _lib.check(rc, "dsm_fill_background")
     return out

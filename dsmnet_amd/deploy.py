@@ -145,9 +145,34 @@ def evaluate_pair(imgL_np, imgR_np, disp, path_disp_gt, flip=False):
                     np.ascontiguousarray(gt)[None, None])
 
 
-def main(argv=None):
-    from .img_rw import imread
-    from .models import model_create_by_name
+def lr_predict(model, imgL_np, imgR_np, threshold=1.0, fill=False):
+    """``disp_predict`` of both views with the left-right check (``postprocess.left_right_check``): the
+    images go through the same preparation; the dict's (H,W) maps come back as numpy arrays, masks as bool."""
+    from .postprocess import left_right_check
+    transform = Stereo_normalize()
+    prep = lambda im: transform(torch.from_numpy(im.copy().transpose(2, 0, 1)[None]).float().cuda() / 255.0)
+    res = left_right_check(model, prep(imgL_np), prep(imgR_np), threshold=threshold, fill=fill)
+    return {k: (v[0, 0] if v.dim() == 4 else v[0]).cpu().numpy() for k, v in res.items()}
+
+
+def evaluate_consistent(imgL_np, imgR_np, disp, mask, path_disp_gt, flip=False):
+    """``evaluate_pair`` over the consistent pixels only: the ground truth is zeroed (a hole) where ``mask``
+    is false.  ``disp`` / ``mask`` / the file are the predicted view's, as for ``evaluate_pair``."""
+    from .evaluate import evaluate
+    from .img_rw import load_disp
+    gt = np.asarray(load_disp(path_disp_gt), dtype=np.float32)
+    if gt.shape != disp.shape:
+        raise ValueError("ground truth %s does not match the prediction %s" % (gt.shape, disp.shape))
+    gt = np.where(mask, gt, np.float32(0))
+    if flip:
+        imgL_np, imgR_np = np.flip(imgR_np, axis=1), np.flip(imgL_np, axis=1)
+        disp, gt = np.flip(disp, axis=-1), np.flip(gt, axis=-1)
+    chw = lambda im: np.ascontiguousarray(im, dtype=np.float32).transpose(2, 0, 1)[None] / 255.0
+    return evaluate(chw(imgL_np), chw(imgR_np), np.ascontiguousarray(disp, dtype=np.float32)[None, None],
+                    np.ascontiguousarray(gt)[None, None])
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description="stereo matching, single pair (MI355X)")
     ap.add_argument("--net", default="dispnetcorr", type=str,
                     help="dispnet / dispnetcorr / iresnet / gcnet / psmnet")
@@ -161,19 +186,45 @@ def main(argv=None):
     ap.add_argument("--path_disp_gt", default=None, type=str,
                     help="ground-truth disparity of the predicted view (PFM or PNG): print D1, EPE and "
                          "the photometric error (utils/evaluate.py evaluate)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--lr_check", action="store_true",
+                    help="predict both views, check them against each other and write <stem>_mask.png "
+                         "next to the disparity (white: consistent)")
+    ap.add_argument("--lr_threshold", default=1.0, type=float,
+                    help="largest left-right disagreement of a consistent pixel, in pixels")
+    ap.add_argument("--fill", action="store_true",
+                    help="with --lr_check: write the disparity with the inconsistent pixels filled from "
+                         "the background")
+    return ap
+
+
+def main(argv=None):
+    from .img_rw import imread
+    from .models import model_create_by_name
+    args = build_parser().parse_args(argv)
+    if args.fill and not args.lr_check:
+        raise SystemExit("--fill needs --lr_check")
     if not torch.cuda.is_available():
         raise SystemExit("dsmnet_amd.deploy needs an MI355X: the HIP path has no CPU fallback")
     imgL, imgR = imread(args.path_left), imread(args.path_right)
     model = model_create_by_name(args.net, args.maxdisparity)
     load_weights(model, args.path_weight)
     model = model.eval().cuda()
-    if args.flip:
+    mask = None
+    if args.lr_check:
+        side = "R" if args.flip else "L"
+        res = lr_predict(model, imgL, imgR, args.lr_threshold, args.fill)
+        raw, mask, out = res["disp" + side], res["mask" + side], args.out or "disp%s.png" % side
+        disp = res["filled" + side] if args.fill else raw
+        if args.path_disp_gt:
+            print("D1 %.4f %%  EPE %.4f px  pixelerror %.4f" % evaluate_pair(imgL, imgR, raw, args.path_disp_gt, args.flip))
+            print("consistent pixels (%.2f %%): D1 %.4f %%  EPE %.4f px  pixelerror %.4f"
+                  % ((100.0 * mask.mean(),) + tuple(evaluate_consistent(imgL, imgR, raw, mask, args.path_disp_gt, args.flip))))
+    elif args.flip:
         disp = disp_predict(model, np.flip(imgR, axis=1), np.flip(imgL, axis=1), True)
         disp, out = np.flip(disp, axis=-1), args.out or "dispR.png"
     else:
         disp, out = disp_predict(model, imgL, imgR, True), args.out or "dispL.png"
-    if args.path_disp_gt:
+    if args.path_disp_gt and mask is None:
         print("D1 %.4f %%  EPE %.4f px  pixelerror %.4f" % evaluate_pair(imgL, imgR, disp, args.path_disp_gt, args.flip))
     if out.endswith(".pfm"):
         from .img_rw import save_pfm
@@ -181,6 +232,9 @@ def main(argv=None):
     else:
         import matplotlib.pyplot as plt
         plt.imsave(out, disp)
+    if mask is not None:
+        import matplotlib.pyplot as plt
+        plt.imsave(os.path.splitext(out)[0] + "_mask.png", mask.astype(np.uint8) * 255, cmap="gray", vmin=0, vmax=255)
     return out
 
 

@@ -1,0 +1,59 @@
+"""Post-processing of predicted disparity maps on the device: the left-right consistency check of both
+views and the background fill of the pixels it rejects (csrc/lrcheck.hip, ``costvolume.lr_check`` and
+``costvolume.fill_background``).
+
+The check is the one the ``-mask`` objectives train with (losses/loss.py:451-455: each view's map is
+compared with the other view's map warped by ``imwrap_BCHW(.., fliplr=True)``); the right view is
+predicted as ``deploy --flip`` does it, from the mirrored and swapped pair (stereo.py:142-150).
+"""
+import torch
+
+from . import costvolume as cv
+
+
+def _first_map(out):
+    """The full-resolution map of a forward's result: ``(loss, [disp, ...])`` of the factory's networks."""
+    _, disps = out
+    return disps[0]
+
+
+def _is_lr_pair(out):
+    """``gcnet_LR``'s return convention: a pair of tensors ``(oL, oR)``, each in its own camera's frame."""
+    return isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(t) for t in out)
+
+
+def left_right_check(model, imL, imR, threshold=1.0, fill=True):
+    """Both views' disparity, consistency mask and weight, and the filled maps, of one batch.
+
+    ``model``: a network of the factory (``forward(imL, imR) -> (_, [disp, ...])``, the first map (B,1,H,W)
+    or PSMNet's (B,H,W)), run twice -- on the pair and on the mirrored, swapped pair
+    ``(flip(imR), flip(imL))`` -- or one with ``gcnet_LR``'s convention ``forward(imL, imR) -> (oL, oR)``,
+    run once.  Eval mode, no gradients, one ``amax_scope``.  ``imL`` / ``imR``: (B,3,H,W) on the device, as
+    the network expects them (normalised or not).
+
+    Returns a dict of device tensors shaped like the network's map:
+      dispL, dispR      the two views' maps, each in its own camera's frame
+      maskL, maskR      ``torch.bool``: |d - warped other view| < ``threshold`` and the sample inside
+      weightL, weightR  the reference's soft weight (loss.py:393-404), factor 1
+      filledL, filledR  with ``fill``: the maps with the rejected pixels filled from the background
+    The right view is checked in the mirrored frame (loss.py:452) and its results are flipped back."""
+    flip = lambda t: torch.flip(t, dims=[-1])
+    want = ("weight", "mask")
+    model.eval()
+    with torch.no_grad(), cv.amax_scope(imL.device):
+        out = model(imL, imR)
+        if _is_lr_pair(out):
+            dL, dR = out[0].contiguous(), out[1].contiguous()
+            dRm = flip(dR)
+            left = cv.lr_check(dL, dR, mirrored=False, threshold=threshold, want=want)
+        else:
+            dL = _first_map(out).contiguous()
+            dRm = _first_map(model(flip(imR), flip(imL))).contiguous()
+            left = cv.lr_check(dL, dRm, mirrored=True, threshold=threshold, want=want)
+        right = cv.lr_check(dRm, dL, mirrored=True, threshold=threshold, want=want)
+        res = {"dispL": dL, "dispR": flip(dRm), "maskL": left.mask, "maskR": flip(right.mask),
+               "weightL": left.weight, "weightR": flip(right.weight)}
+        if fill:
+            res["filledL"] = cv.fill_background(dL, left.mask)
+            res["filledR"] = flip(cv.fill_background(dRm, right.mask))
+    return res

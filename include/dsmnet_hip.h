@@ -752,6 +752,61 @@ typedef struct dsm_metrics_args {
 size_t dsm_stereo_metrics_workspace_bytes(int B, int H, int W);
 int dsm_stereo_metrics(const dsm_metrics_args* args, dsm_stream_t stream);
 
+/* (ABI v7, additive) Left-right consistency check of a disparity map (csrc/lrcheck.hip) -- the warp of
+ * utils/imwrap.py:37-72 imwrap_BCHW(other, disp, fliplr=True, LeftTop=[0,0], scale_factor=1) as
+ * losses/loss.py:451-452 call it, and the weight of losses/loss.py:393-404 weight_common.
+ * disp, other: (B,H,W) fp32 contiguous (a (B,1,H,W) map is the same memory).  One launch, no atomics, no
+ * host synchronisation.  Per pixel, in fp32:
+ *    wrap    other sampled with grid_sample(bilinear, zeros, align_corners=False) at
+ *            x = -(linspace(-1, 1, W)[x] - disp * 2 / (W - 1)), y = linspace(-1, 1, H)[y];
+ *            delt (the reference's random epsilon, drawn by the caller; 0 for inference) is added to
+ *            the in-bounds taps only
+ *    delta   |disp - wrap| / factor
+ *    weight  1 for delta < 1, 1 - (delta - 1) * (0.99 / 2) for 1 <= delta < 3, 0.01 from 3 on
+ *    mask    uint8, 1 where delta < threshold and the sample position ix = ((gx + 1) * W - 1) / 2 of that x coordinate gx lies in
+ *            [0, W - 1] (beyond the reference: a sample half out of the image is no measurement), else 0
+ *    masked  disp where mask is set, else 0
+ * Each of wrap, weight, mask, masked may be NULL, not all four.
+ * flags: 0 -- other is in the mirrored frame (predicted from the mirrored, swapped pair, as dispL1 of
+ * loss.py:451) -- or DSM_LRCHECK_OTHER_RIGHT_FRAME: other is the right camera's map in its own frame
+ * and is read at column W - 1 - x, without a copy; bit-identical to flags 0 on the mirrored map.
+ * DSM_ERR_ARG (nothing launched): NULL args, disp or other; all four outputs NULL; B <= 0; H or W < 2
+ * (imwrap.py:48); a factor that is not finite and positive; a threshold that is not finite; any other
+ * flags bit.  DSM_ERR_ALIGN: an fp32 map that is not 4-byte aligned.  DSM_ERR_UNSUPPORTED: 2^31 tiles of
+ * 16x64 or more.  sizeof(dsm_lrcheck_args) == 80. */
+#define DSM_LRCHECK_OTHER_RIGHT_FRAME 1
+typedef struct dsm_lrcheck_args {
+  const void* disp;
+  const void* other;
+  void* wrap;
+  void* weight;
+  void* mask;
+  void* masked;
+  int B, H, W;
+  float delt;
+  float factor;
+  float threshold;
+  int flags;
+  int reserved;
+} dsm_lrcheck_args;
+
+int dsm_lr_check(const dsm_lrcheck_args* args, dsm_stream_t stream);
+
+/* (ABI v7, additive) Background fill of the pixels a mask rejects (csrc/lrcheck.hip).  disp (B,H,W) fp32,
+ * mask (B,H,W) uint8 (non-zero: valid), out (B,H,W) fp32.  Two launches, no atomics, no host
+ * synchronisation; the value of an invalid pixel is never read.
+ *   rows        a valid pixel is copied; an invalid one gets fminf of the nearest valid pixels to its
+ *               left and right in its row, or the one that exists; a row without a valid pixel is empty
+ *   empty rows  element by element, fminf of the nearest non-empty rows above and below as filled, or the
+ *               one that exists; an image without a valid pixel becomes zeros
+ * workspace: dsm_fill_background_workspace_bytes(B, H, W) bytes = B * H * 4 (0 for non-positive sizes),
+ * fully overwritten.
+ * DSM_ERR_ARG (nothing launched): a NULL pointer; B, H or W <= 0; out overlapping disp, mask or the
+ * workspace.  DSM_ERR_ALIGN: disp, out or workspace not 4-byte aligned.  DSM_ERR_UNSUPPORTED: B * H >= 2^31. */
+size_t dsm_fill_background_workspace_bytes(int B, int H, int W);
+int dsm_fill_background(const void* disp, const void* mask, void* out, void* workspace, int B, int H, int W,
+                        dsm_stream_t stream);
+
 /* (ABI v7, additive) Stereo colour augmentation of a training batch, fused -- replaces
  * myTransforms/__init__.py:109-135 Stereo_color / Stereo_normalize applied by Stereo_color_batch,
  * i.e. myTransforms/aug_color.py ColorJitter (RandomOrder :175-203 over Brightness, Contrast,
