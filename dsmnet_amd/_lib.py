@@ -130,6 +130,21 @@ class SpatialRecord(ctypes.Structure):
 DSM_SPATIAL_MAX_RECORDS = 48
 
 
+class FrameSource(ctypes.Structure):
+    """struct dsm_frame_source (include/dsmnet_hip.h), 64 bytes."""
+    _fields_ = [("imL", ctypes.c_longlong), ("imR", ctypes.c_longlong),
+                ("dispL", ctypes.c_longlong), ("dispR", ctypes.c_longlong),
+                ("Hs", c_int), ("Ws", c_int), ("y0", c_int), ("x0", c_int),
+                ("flip", c_int), ("disp_format", c_int), ("pad_", c_int * 2)]
+
+
+DSM_DISP_F32 = 0
+DSM_DISP_U16_256 = 1
+DSM_DISP_U16 = 2
+DSM_DISP_U8 = 3
+DSM_FRAMES_MAX_RECORDS = 32
+
+
 # name -> (restype, argtypes); must list every symbol declared in dsmnet_hip.h
 SIGNATURES = {
     "dsm_abi_version": (c_int, []),
@@ -194,6 +209,10 @@ SIGNATURES = {
     "dsm_fill_background": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
     "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),
     "dsm_stereo_spatial": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SpatialRecord)] + [c_int] * 8 + [c_void_p]),
+    "dsm_stereo_spatial_raw": (c_int, [c_void_p, c_size_t, ctypes.POINTER(FrameSource), c_void_p,
+                                       ctypes.POINTER(SpatialRecord)] + [c_int] * 8 + [c_void_p]),
+    "dsm_stereo_spatial_raw_plan": (c_int, [c_void_p, c_size_t, ctypes.POINTER(FrameSource), c_void_p,
+                                            ctypes.POINTER(SpatialRecord)] + [c_int] * 8),
     "dsm_concat_conv_fwd": (c_int, [c_void_p] * 5 + [c_size_t] + [c_void_p] * 2 + [c_int] * 9 + [c_void_p]),
 }
 

@@ -2212,6 +2212,72 @@ def stereo_spatial(x, records, out_hw, to_tensor_channels=6):
     return y
 
 
+_DISP_BYTES = {_lib.DSM_DISP_F32: 4, _lib.DSM_DISP_U16_256: 2, _lib.DSM_DISP_U16: 2, _lib.DSM_DISP_U8: 1}
+
+
+def stereo_spatial_raw(raw, sources, records, frame_hw, C, out_hw, to_tensor_channels=6):
+    """``stereo_spatial`` from the decoded files' bytes: the (B,C,h,w) training batch of B samples
+    whose planes lie in the 1-D uint8 device tensor ``raw`` as decoded -- (Hs,Ws,3) uint8 RGB,
+    (Hs,Ws) uint8 / uint16 / float32 disparity -- without forming the fp32 frames (csrc/frames.hip;
+    myDatasets_stereo/Dataset_stereo.py:63-74, 86-99, 121-123, then aug_spatial.py:7-88 and
+    aug_color.py:15-26).  ``sources``: B tuples ``(imL, imR, dispL, dispR, Hs, Ws, y0, x0, flip,
+    disp_format)`` in the field order of ``dsm_frame_source`` (byte offsets into ``raw``, -1 for an
+    absent disparity; ``disp_format`` one of ``_lib.DSM_DISP_*``): frame pixel (y, x) of the
+    ``frame_hw`` = (H0, W0) frame is source pixel (y0 + y, x0 + (W0 - 1 - x if flip else x)).
+    ``records``, ``out_hw`` and ``to_tensor_channels`` as for ``stereo_spatial``, and the result is
+    bit-identical to it on frames assembled on the host.  One launch per 32 images, on the current
+    stream, no host synchronisation.  Returns the new batch."""
+    if not raw.is_cuda:
+        _require_device("stereo_spatial_raw", raw)
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or not raw.is_contiguous():
+        raise ValueError("stereo_spatial_raw: raw must be a dense 1-D uint8 tensor, got %s %s"
+                         % (raw.dtype, tuple(raw.shape)))
+    C = int(C)
+    if not 6 <= C <= 8:
+        raise ValueError("stereo_spatial_raw: 6 <= C <= 8 (imL | imR [| dispL [| dispR]]), got %d" % C)
+    if to_tensor_channels not in (0, 6):
+        raise ValueError("stereo_spatial_raw: to_tensor_channels must be 0 or 6, got %r" % (to_tensor_channels,))
+    B = len(sources)
+    H0, W0 = int(frame_hw[0]), int(frame_hw[1])
+    h, w = int(out_hw[0]), int(out_hw[1])
+    if B < 1 or H0 < 1 or W0 < 1 or h < 1 or w < 1:
+        raise ValueError("stereo_spatial_raw: empty batch, frame or output (B = %d, frame_hw = %s, out_hw = %s)"
+                         % (B, (H0, W0), (h, w)))
+    if len(records) != B:
+        raise ValueError("stereo_spatial_raw: %d records for %d images" % (len(records), B))
+    srcs = (_lib.FrameSource * B)()
+    nbytes = 0
+    for s, (imL, imR, dispL, dispR, Hs, Ws, y0, x0, flip, disp_format) in zip(srcs, sources):
+        s.imL, s.imR, s.dispL, s.dispR = int(imL), int(imR), int(dispL), int(dispR)
+        s.Hs, s.Ws, s.y0, s.x0 = int(Hs), int(Ws), int(y0), int(x0)
+        s.flip, s.disp_format = int(flip), int(disp_format)
+        nbytes += 6 + (C - 6) * _DISP_BYTES.get(s.disp_format, 0)
+    recs = (_lib.SpatialRecord * B)()
+    for r, (shift, ws, hs, rw, rh, resize, scale_rand, scale_x, scale_y) in zip(recs, records):
+        r.shift, r.ws, r.hs, r.w, r.h = int(shift), int(ws), int(hs), int(rw), int(rh)
+        r.resize, r.scale_rand = int(bool(resize)), float(scale_rand)
+        r.scale_x, r.scale_y = float(scale_x), float(scale_y)
+    y = torch.empty(B, C, h, w, device=raw.device, dtype=torch.float32)
+    lib = _lib.load()
+    step = _lib.DSM_FRAMES_MAX_RECORDS
+    with torch.cuda.device(raw.device):
+        # validate the whole batch before the first launch: a refused call leaves y untouched
+        _lib.check(lib.dsm_stereo_spatial_raw_plan(_p(raw), raw.numel(), srcs, _p(y), recs, B, B, C, H0, W0, h, w,
+                                                   int(to_tensor_channels)), "dsm_stereo_spatial_raw")
+        for b0 in range(0, B, step):
+            nb = min(step, B - b0)
+            yb = y[b0:b0 + nb]
+            with _timed("stereo_spatial_raw_kernel", (float(nbytes) / B + 4.0 * C) * nb * h * w):
+                rc = lib.dsm_stereo_spatial_raw(
+                    _p(raw), raw.numel(), ctypes.cast(ctypes.byref(srcs, b0 * ctypes.sizeof(_lib.FrameSource)),
+                                                      ctypes.POINTER(_lib.FrameSource)), _p(yb),
+                    ctypes.cast(ctypes.byref(recs, b0 * ctypes.sizeof(_lib.SpatialRecord)),
+                                ctypes.POINTER(_lib.SpatialRecord)), nb, nb, C, H0, W0, h, w,
+                    int(to_tensor_channels), _stream())
+            _lib.check(rc, "dsm_stereo_spatial_raw")
+    return y
+
+
 # ----------------------------------------------------------------------------
 # Evaluation metrics: D1 / EPE, the KITTI set, photometric error (csrc/metrics.hip)
 # ----------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include "common.hpp"
+#include "spatial_taps.hpp"
 
 #pragma clang fp contract(off)
 
@@ -28,16 +29,6 @@ namespace {
 struct SpatialRecords {
   dsm_spatial_record r[DSM_SPATIAL_MAX_RECORDS];
 };
-
-// cv2's linear-resize coordinate of output index d: tap s in [0, n), weight f of tap min(s+1, n-1)
-__device__ __forceinline__ void resize_tap(int d, double scale, int n, int& s, float& f) {
-  f = (float)(((double)d + 0.5) * scale - 0.5);
-  const float fl = floorf(f);
-  s = (int)fl;
-  f -= fl;
-  if (s < 0) { s = 0; f = 0.f; }
-  if (s >= n - 1) { s = n - 1; f = 0.f; }
-}
 
 // Work item = (image of the chunk, output row, output column); grid-stride over nb * h * w items.
 // C is a template parameter so that the channel loops unroll and every load of a pixel is in flight
@@ -62,15 +53,11 @@ __global__ __launch_bounds__(256) void stereo_spatial_kernel(const float* __rest
       float v[C];
 #pragma unroll
       for (int c = 0; c < C; ++c) {
-        const bool right = (c >= 3 && c < 6) || c == 7;
-        v[c] = src[p + (right ? shift * C : 0) + c];
+        v[c] = src[p + (spatial_right_channel(c) ? shift * C : 0) + c];
       }
 #pragma unroll
-      for (int c = 0; c < C; ++c) {
-        if (c >= 6 && v[c] != 0.f) v[c] += fshift;
-        if (c < to_tensor) v[c] = v[c] / 255.0f;
-        dst[(size_t)c * plane] = v[c];
-      }
+      for (int c = 0; c < C; ++c)
+        dst[(size_t)c * plane] = spatial_finish_crop(v[c], c, fshift, to_tensor);
       continue;
     }
     int sx, sy;
@@ -84,40 +71,17 @@ __global__ __launch_bounds__(256) void stereo_spatial_kernel(const float* __rest
     float t[C][4];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const bool right = (c >= 3 && c < 6) || c == 7;
-      const int o = (right ? shift * C : 0) + c;
+      const int o = (spatial_right_channel(c) ? shift * C : 0) + c;
       t[c][0] = src[(r0 + c0) * C + o];
       t[c][1] = src[(r0 + c1) * C + o];
       t[c][2] = src[(r1 + c0) * C + o];
       t[c][3] = src[(r1 + c1) * C + o];
     }
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-      float t00 = t[c][0], t01 = t[c][1], t10 = t[c][2], t11 = t[c][3];
-      if (c >= 6) {
-        if (t00 != 0.f) t00 += fshift;
-        if (t01 != 0.f) t01 += fshift;
-        if (t10 != 0.f) t10 += fshift;
-        if (t11 != 0.f) t11 += fshift;
-      }
-      const float a = t00 * gx + t01 * fx;
-      const float b = t10 * gx + t11 * fx;
-      float v = a * gy + b * fy;
-      if (c >= 6) v = v * rec.scale_rand;
-      if (c < to_tensor) v = v / 255.0f;
-      dst[(size_t)c * plane] = v;
-    }
+    for (int c = 0; c < C; ++c)
+      dst[(size_t)c * plane] = spatial_finish_resize(t[c][0], t[c][1], t[c][2], t[c][3], c, fshift, gx, fx, gy, fy,
+                                                     rec.scale_rand, to_tensor);
   }
-}
-
-bool spatial_record_ok(const dsm_spatial_record& r, int H0, int W0, int h, int w) {
-  if (r.shift < 0 || r.shift >= W0) return false;
-  if (r.w < 1 || r.h < 1 || r.ws < 0 || r.hs < 0) return false;
-  if ((long)r.ws + r.w > (long)W0 - r.shift || (long)r.hs + r.h > (long)H0) return false;
-  if (r.resize != 0 && r.resize != 1) return false;
-  if (!r.resize) return r.w == w && r.h == h;
-  return isfinite(r.scale_x) && isfinite(r.scale_y) && r.scale_x > 0 && r.scale_y > 0 &&
-         isfinite(r.scale_rand);
 }
 
 }  // namespace

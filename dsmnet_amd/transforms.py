@@ -37,6 +37,10 @@ skips.  With ``scale_delt == 0`` the reference's output width is min(W0 - shift,
 differ per image; ``ValueError`` when W0 - (shift_max - 1) < w1, as the batch could otherwise not
 be rectangular.  The resize is cv2's linear rule as stated in DESIGN.md §13b; that it equals the
 cv2 binary is not measured.
+
+``Compose.call_raw`` is the same pipeline started from the decoded files' bytes instead of fp32
+frames (``costvolume.stereo_spatial_raw``, csrc/frames.hip); ``datasets.DeviceLoader``
+is its caller.
 """
 import random
 
@@ -258,6 +262,30 @@ class Compose(object):
             hw = self.spatial.out_hw(H0, W0)
             records = [self.spatial.draw(H0, W0) for _ in range(B)]
         return records, hw, self.to_tensor.channel if self.to_tensor is not None else 0
+
+    def call_raw(self, raw, sources, frame_hw, C, draw_flip=None):
+        """The hook of ``datasets.DeviceLoader``: plan for ``len(sources)`` frames of ``frame_hw`` =
+        (H0, W0), then launch from the decoded files' bytes instead of from fp32 frames
+        (``costvolume.stereo_spatial_raw``; ``raw`` and ``sources`` as there), then the colour
+        launches on the result.  ``draw_flip()`` -> 0 / 1, if given, is called once per image
+        right before that image's spatial numbers are drawn and overrides the source's ``flip``:
+        the order of the reference's loop (Dataset_stereo.py:122, then the transform).  Returns
+        the new (B, C, h, w) batch, bit-identical to ``__call__`` on the assembled frames."""
+        if self.spatial is None and self.to_tensor is None:
+            raise TypeError("Compose.call_raw: the sequence must be led by Spatial_stereo and / or ToTensor_numpy")
+        H0, W0 = int(frame_hw[0]), int(frame_hw[1])
+        hw = self.spatial.out_hw(H0, W0) if self.spatial is not None else (H0, W0)
+        records, sources = [], [tuple(s) for s in sources]
+        for i, s in enumerate(sources):
+            if draw_flip is not None:
+                sources[i] = s[:8] + (int(draw_flip()),) + s[9:]
+            records.append(self.spatial.draw(H0, W0) if self.spatial is not None
+                           else (0, 0, 0, W0, H0, 0, 1.0, 1.0, 1.0))
+        out = cv.stereo_spatial_raw(raw, sources, records, (H0, W0), C, hw,
+                                    self.to_tensor.channel if self.to_tensor is not None else 0)
+        for records, alpha, G in self.plan(out.shape[0], out.shape[1], out.device, out.dtype):
+            cv.stereo_color(out, records, alpha, G)
+        return out
 
     def _call_spatial(self, img):
         if img.dim() not in (3, 4):

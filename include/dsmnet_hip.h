@@ -874,6 +874,54 @@ typedef struct dsm_spatial_record {
 int dsm_stereo_spatial(const void* x, void* y, const dsm_spatial_record* recs, int n_recs, int B, int C,
                        int H0, int W0, int h, int w, int to_tensor_channels, dsm_stream_t stream);
 
+/* (ABI v7, additive) dsm_stereo_spatial from the decoded files' bytes (csrc/frames.hip, DESIGN.md
+ * 13c) -- additionally replaces what myDatasets_stereo/Dataset_stereo.py does on the host in
+ * __getitem__: :63-74 Crop_center_bottom, :86-99 np.float32 and the channel concatenation, :121-123
+ * the horizontal flip.  The (B, H0, W0, C) fp32 frames are never formed.
+ *   raw   raw_bytes bytes on the device holding every sample's planes as decoded:
+ *         imL, imR   (Hs, Ws, 3) uint8 RGB, dense, at any byte offset;
+ *         dispL/R    (Hs, Ws) per disp_format: DSM_DISP_F32 float32 (a non-finite value reads as
+ *                    0, as img_rw.load_gray makes it), DSM_DISP_U16_256 uint16 / 256.0f (KITTI's
+ *                    encoding), DSM_DISP_U16 (float)uint16, DSM_DISP_U8 (float)uint8;
+ *                    read only for C >= 7 (dispL) and C == 8 (dispR), -1 otherwise
+ *   srcs  one per image: frame pixel (y, x, c) is the source pixel at row y0 + y, column
+ *         x0 + (flip ? W0 - 1 - x : x) of imL (c < 3), imR (3 <= c < 6), dispL (6), dispR (7).
+ *         The flip mirrors every channel and does not swap the views.
+ *   y, recs, h, w, to_tensor_channels   as for dsm_stereo_spatial, applied to that frame; the
+ *         float sequence is the same, so y is bit-identical to dsm_stereo_spatial on fp32 frames
+ *         assembled on the host (uint8 -> float and uint16 / 256 are exact).
+ * DSM_ERR_ARG (nothing launched): everything dsm_stereo_spatial refuses for the records; a null
+ * pointer; C >= 7 with dispL < 0, C == 8 with dispR < 0; an unknown disp_format; flip not 0 or 1;
+ * y0 or x0 negative or a frame that does not fit Hs x Ws; a plane not wholly inside
+ * [0, raw_bytes).  DSM_ERR_UNSUPPORTED: one plane, one (fp32) frame or one output image of 2^31
+ * bytes or more.  DSM_ERR_ALIGN: y not 4-byte aligned, a uint16 plane at an odd address, a float32
+ * plane not 4-byte aligned.  Because every plane is checked against raw_bytes, the kernel cannot
+ * read outside raw.  Sources and records travel in kernel arguments, 112 B per image,
+ * DSM_FRAMES_MAX_RECORDS per launch (larger batches: one launch per chunk); no host
+ * synchronisation.  dsm_stereo_spatial_raw_plan runs the same checks and launches nothing.
+ * sizeof(dsm_frame_source) == 64. */
+#define DSM_DISP_F32 0
+#define DSM_DISP_U16_256 1
+#define DSM_DISP_U16 2
+#define DSM_DISP_U8 3
+#define DSM_FRAMES_MAX_RECORDS 32
+typedef struct dsm_frame_source {
+  long long imL, imR;     /* byte offsets into raw */
+  long long dispL, dispR; /* byte offsets into raw, or -1 */
+  int Hs, Ws;             /* this sample's file size (all its planes) */
+  int y0, x0;             /* top-left of the H0 x W0 frame inside it */
+  int flip;
+  int disp_format;
+  int pad_[2];
+} dsm_frame_source;
+
+int dsm_stereo_spatial_raw(const void* raw, size_t raw_bytes, const dsm_frame_source* srcs, void* y,
+                           const dsm_spatial_record* recs, int n_recs, int B, int C, int H0, int W0, int h,
+                           int w, int to_tensor_channels, dsm_stream_t stream);
+int dsm_stereo_spatial_raw_plan(const void* raw, size_t raw_bytes, const dsm_frame_source* srcs, void* y,
+                                const dsm_spatial_record* recs, int n_recs, int B, int C, int H0, int W0,
+                                int h, int w, int to_tensor_channels);
+
 /* (ABI v7, additive) First convolution of a concatenation cost volume, from 2-D maps (csrc/sepvol.hip,
  * DESIGN.md 3.2f): y = relu?(conv3d(volume, W; k3 s1 p1) * scale + shift) for the volume of
  * dsm_concat_volume_fwd, which is never formed -- plane d is [left | right shifted by d], so the
