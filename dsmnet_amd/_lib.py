@@ -165,6 +165,8 @@ SIGNATURES = {
     "dsm_concat_volume_bwd_plan": (c_int, [c_void_p] * 3 + [c_int] * 8 + [ctypes.c_char_p, c_int]),
     "dsm_soft_argmin_fwd_plan": (c_int, [c_void_p] * 3 + [c_int] * 10 + [ctypes.c_char_p, c_int]),
     "dsm_soft_argmin_bwd_plan": (c_int, [c_void_p] * 5 + [c_int] * 10 + [ctypes.c_char_p, c_int]),
+    "dsm_disp_confidence_fwd": (c_int, [c_void_p] * 6 + [c_int] * 11 + [c_void_p]),
+    "dsm_disp_confidence_fwd_plan": (c_int, [c_void_p] * 6 + [c_int] * 11 + [ctypes.c_char_p, c_int]),
     "dsm_conv3d_packed_weight_bytes": (c_size_t, [c_int] * 3),
     "dsm_conv3d_pack_weights": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
     "dsm_conv_pack_weights": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),

@@ -16,6 +16,7 @@ Reference code each op replaces (sunshinnnn/DSMnet):
   supervised_pyramid_loss   losses/loss.py:326-338, 407-421, stereo.py:103-113
   stereo_metrics  utils/evaluate.py:9-73, stereo.py:103-113, utils/imwrap.py:37-72
   lr_check        utils/imwrap.py:37-72 (fliplr=True), losses/loss.py:393-404, 451-452
+  soft_argmin_confidence   the softmax of the two soft_argmin sites above, kept for its peak, window and entropy
 """
 import collections
 import ctypes
@@ -129,6 +130,12 @@ def soft_argmin_bwd_plan_name(cost, disp, stats, gdisp, dcost, B, Dc, Hc, Wc, D,
     """Kernel ``dsm_soft_argmin_bwd`` picks: ``bwd_direct``, ``bwd_tile nseg=N`` or ``bwd_fallback``."""
     return _plan_name("dsm_soft_argmin_bwd_plan", cost, disp, stats, gdisp, dcost, B, Dc, Hc, Wc, D, H, W,
                       int(negate), int(align_corners), _lib.DSM_F32)
+
+
+def confidence_plan_name(cost, disp, B, Dc, Hc, Wc, D, H, W, negate=False, align_corners=False, radius=4):
+    """Kernel ``dsm_disp_confidence_fwd`` picks: ``conf_up4<4>``, ``conf<true,DS>`` or ``conf<false,DS>``."""
+    return _plan_name("dsm_disp_confidence_fwd_plan", cost, disp, None, None, None, None, B, Dc, Hc, Wc, D, H, W,
+                      int(negate), int(align_corners), int(radius), _lib.DSM_F32)
 
 
 def _require_device(name, *tensors):
@@ -404,6 +411,61 @@ def soft_argmin_kernel_label(plan):
 def soft_argmin(cost, out_size=None, negate=False, align_corners=False):
     """Fused (trilinear upsample ->) softmax over disparity -> expectation.  -> (B, H, W)."""
     return SoftArgminFunction.apply(cost, out_size, bool(negate), bool(align_corners))
+
+
+DispConfidence = collections.namedtuple("DispConfidence", ("disp", "peak", "pmax", "pwin", "entropy"))
+
+
+def soft_argmin_confidence(cost, out_size=None, negate=False, align_corners=False, radius=4,
+                           want=("peak", "pmax", "pwin", "entropy")):
+    """``soft_argmin`` plus what the softmax it regresses from says about each pixel, in one launch
+    (csrc/soft_argmin.hip, ``dsm_disp_confidence_fwd``).  With ``p`` the softmax over the (upsampled)
+    disparity axis and ``d*`` its first arg-max, all (B, H, W):
+
+      disp     ``sum d p_d``, what ``soft_argmin`` returns
+      peak     the same regression restricted to the window ``[d* - radius, d* + radius]`` (clipped to
+               the range): it does not average across the modes of a bimodal distribution
+      pmax     ``p_{d*}``
+      pwin     the probability mass of that window
+      entropy  ``-sum p_d ln p_d`` in nats, in ``[0, ln D]``
+
+    ``cost``: (B,1,D,H,W) or (B,D,H,W) float32 on the device, as for ``soft_argmin``.  ``want``: the
+    maps to compute besides ``disp``; the others are None.  Inference only: the outputs carry no graph,
+    and a cost that requires grad (with gradients enabled) is refused.  Capturable: torch allocates,
+    nothing synchronises."""
+    _require_device("soft_argmin_confidence", cost)
+    if cost.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("soft_argmin_confidence: inference only, there is no backward for these maps; "
+                           "call it under torch.no_grad() or detach the cost")
+    names = tuple(want)
+    if any(n not in DispConfidence._fields[1:] for n in names):
+        raise ValueError("soft_argmin_confidence: want is a subset of %s, got %r" % (DispConfidence._fields[1:], want))
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError("soft_argmin_confidence: radius must be >= 0, got %d" % radius)
+    if cost.dim() == 5:
+        if cost.shape[1] != 1:
+            raise ValueError("soft_argmin_confidence: 5-D cost must have one channel")
+        c4 = cost.reshape(cost.shape[0], *cost.shape[2:])
+    elif cost.dim() == 4:
+        c4 = cost
+    else:
+        raise ValueError("soft_argmin_confidence: expected (B,1,D,H,W) or (B,D,H,W)")
+    c4 = c4.detach().contiguous()
+    B, Dc, Hc, Wc = c4.shape
+    D, H, W = (Dc, Hc, Wc) if out_size is None else tuple(int(v) for v in out_size)
+    out = {n: torch.empty((B, H, W), device=cost.device, dtype=cost.dtype) for n in ("disp",) + names}
+    lib = _lib.load()
+    kname = lambda: ("disp_confidence_up4_kernel" if confidence_plan_name(
+        c4, out["disp"], B, Dc, Hc, Wc, D, H, W, negate, align_corners, radius).startswith("conf_up4")
+        else "disp_confidence_kernel")
+    with torch.cuda.device(cost.device), _timed(kname, 4.0 * B * (Dc * Hc * Wc + len(out) * H * W)):
+        rc = lib.dsm_disp_confidence_fwd(_p(c4), _p(out["disp"]), _p(out.get("peak")), _p(out.get("pmax")),
+                                         _p(out.get("pwin")), _p(out.get("entropy")), B, Dc, Hc, Wc, D, H, W,
+                                         int(bool(negate)), int(bool(align_corners)), min(radius, 2 ** 31 - 1),
+                                         _lib.DSM_F32, _stream())
+    _lib.check(rc, "dsm_disp_confidence_fwd")
+    return DispConfidence(*[out.get(n) for n in DispConfidence._fields])
 
 
 # ----------------------------------------------------------------------------

@@ -507,6 +507,330 @@ extern "C" int dsm_soft_argmin_fwd(const void* cost, void* disp, void* stats, in
   return dsm_launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Confidence heads (dsm_disp_confidence_fwd): the same distribution, five maps instead of one.
+//   disp = sum d p_d          pmax = p_{d*}, d* the smallest d with v_d = max v
+//   pwin = sum_{Wn} p_d       peak = sum_{Wn} d p_d / pwin,  Wn = [max(0, d* - r), min(D - 1, d* + r)]
+//   entropy = -sum p_d ln p_d = ln l - t / l,  l = sum e_d,  t = sum e_d (v_d - m),  e_d = exp(v_d - m)
+// Same lane layout as the kernels above (64/DSPLIT pixels x DSPLIT segments per wave, merged with
+// __shfl_xor, no LDS); new kernels, the ones above are untouched.  Values stay in natural units (sign times
+// the sample; exponents are scaled by log2 e for v_exp_f32, which is what __expf does): the arg-max compares
+// what the definition compares, and a constant cost stays constant bit for bit.  The running maximum is over
+// fine values in every form, so it IS the arg-max value and the largest term of l is exp(0).
+//
+// Pass A (each lane over its segment) keeps the online (m, l, sum d e) and adds t and the segment's
+// d_best (its value is the running maximum itself).  Every term of t is <= 0: no cancellation.  When the
+// maximum moves from m to m', rho = exp(m - m'):  l <- rho l,  s <- rho s,  t <- rho (t + (m - m') l_old); merging two segments applies
+// the same formulas to both sides; the arg-max keeps the larger value and, on equality, the lower index.
+// Pass B: after the merge every lane of a pixel knows m, l and d*; the <= 2r + 1 bins of the window are
+// evaluated again, split over the pixel's DSPLIT lanes (contiguous runs, so neighbouring bins share their
+// planes) and summed with two more shuffles.  (Measured against the seg == 0 lane walking the whole
+// window alone: 71 against 74 us at radius 4, 79 against 114 us at radius 16; profiles/headconf.md.)
+//
+// Tie rule (contract): wherever both interpolation indices along d coincide -- the clamped top end --
+// the fine value is the plane's value itself, bit for bit, never w0 P + w1 P; at the bottom clamp
+// w1 == 0 and 1 * P + 0 * P' is exact already.  With D = 4 Dc the first two and the last two fine bins
+// are therefore EQUAL and d* is the lower one; rounding never decides.
+struct Cf { float m, l, s, t; int db; };   // running max (= the arg-max value), sum e, sum d e, sum e (v - m), arg-max bin
+
+struct CfParams {
+  SaParams sa;                                 // stats unused
+  float *peak, *pmax, *pwin, *entropy;         // each may be null
+  int radius;                                  // clamped to D by the host
+};
+
+__device__ __forceinline__ Cf cf_neutral() { return Cf{-INFINITY, 0.f, 0.f, 0.f, 0x7fffffff}; }
+
+__device__ __forceinline__ void cf_push(Cf& a, float v, int d) {
+  if (v > a.m) {                                   // strictly larger: the lowest bin of a tie stays
+    const float dm = a.m - v;
+    const float r = __expf(dm);                    // exp(-inf) = 0 on the first bin
+    a.t = (a.m == -INFINITY) ? 0.f : r * fmaf(dm, a.l, a.t);
+    a.l *= r; a.s *= r; a.m = v;
+    a.db = d;
+  }
+  const float u = v - a.m;
+  const float e = __expf(u);
+  a.l += e;
+  a.s = fmaf((float)d, e, a.s);
+  a.t = fmaf(e, u, a.t);
+}
+
+__device__ __forceinline__ Cf cf_merge(const Cf& a, const Cf& b) {
+  Cf o;
+  o.m = fmaxf(a.m, b.m);
+  const bool ea = a.m == -INFINITY, eb = b.m == -INFINITY;     // an empty segment: the neutral element
+  const float da = a.m - o.m, dbm = b.m - o.m;
+  const float ra = ea ? 0.f : __expf(da);
+  const float rb = eb ? 0.f : __expf(dbm);
+  o.l = a.l * ra + b.l * rb;
+  o.s = a.s * ra + b.s * rb;
+  o.t = (ea ? 0.f : ra * fmaf(da, a.l, a.t)) + (eb ? 0.f : rb * fmaf(dbm, b.l, b.t));
+  o.db = (b.m > a.m || (b.m == a.m && b.db < a.db)) ? b.db : a.db;
+  return o;
+}
+
+__device__ __forceinline__ Stencil cf_stencil(const SaParams& p, int y, int x, int align) {
+  const Lerp ly = lerp_at(y, p.sh, p.Hc, p.H, align);
+  const Lerp lx = lerp_at(x, p.sw, p.Wc, p.W, align);
+  Stencil st;
+  st.o00 = ly.i0 * p.Wc + lx.i0; st.o01 = ly.i0 * p.Wc + lx.i1;
+  st.o10 = ly.i1 * p.Wc + lx.i0; st.o11 = ly.i1 * p.Wc + lx.i1;
+  st.wy0 = ly.w0; st.wy1 = ly.w1; st.wx0 = lx.w0; st.wx1 = lx.w1;
+  return st;
+}
+
+// plane_at with every rounding spelled out.  Pass B evaluates the window's bins a second time and must get
+// pass A's values bit for bit (the arg-max bin's term is exp(0) in both); left to the compiler, the
+// contraction of plane_at's products and sums into fused multiply-adds may differ from one inlined copy
+// to the next.
+__device__ __forceinline__ float cf_plane(const float* __restrict__ base, long plane_stride, int k,
+                                          const Stencil& st) {
+  const float* p = base + (long)k * plane_stride;
+  const float r0 = fmaf(st.wx1, p[st.o01], st.wx0 * p[st.o00]);
+  const float r1 = fmaf(st.wx1, p[st.o11], st.wx0 * p[st.o10]);
+  return fmaf(st.wy1, r1, st.wy0 * r0);
+}
+
+// One segment of the x4 head, bins 4 k_lo .. 4 k_hi - 1, on pairs of bins with packed fp32 instructions (the
+// weights: see soft_argmin_up4_kernel).  Unlike that kernel, the running maximum is over the FINE values --
+// the arg-max needs them anyway, with the tie rule at k == 0 and k == Dc - 1 -- so the largest term is always
+// exp(0): no segment can underflow (no exact fallback), and ln l and t / l carry no common offset that would
+// cancel in the entropy.  The four values of a plane are known before its exponentials, so the maximum is
+// raised first and every exponent is <= 0.
+__device__ __forceinline__ Cf cf_up4_segment(const float* __restrict__ base, long ps, const Stencil& st,
+                                             float sg, int k_lo, int k_hi, int Dc) {
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  constexpr float LOG2E = 1.4426950408889634f;
+  float Pm = sg * cf_plane(base, ps, max(k_lo - 1, 0), st);
+  float Pc = sg * cf_plane(base, ps, k_lo, st);
+  float m = -INFINITY;
+  f2 l2 = {0.f, 0.f}, s2 = {0.f, 0.f}, t2 = {0.f, 0.f};
+  f2 d01 = {(float)(4 * k_lo), (float)(4 * k_lo + 1)}, d23 = {(float)(4 * k_lo + 2), (float)(4 * k_lo + 3)};
+  const f2 ca = {0.375f, 0.125f}, cb = {0.625f, 0.875f}, four = {4.f, 4.f}, log2e = {LOG2E, LOG2E};
+  int db = 0x7fffffff;
+  for (int k = k_lo; k < k_hi; ++k) {
+    const float Pn = sg * cf_plane(base, ps, min(k + 1, Dc - 1), st);
+    const f2 pc = cb * f2{Pc, Pc};
+    f2 a01 = __builtin_elementwise_fma(ca, f2{Pm, Pm}, pc);  // bins 4k, 4k+1
+    f2 a32 = __builtin_elementwise_fma(ca, f2{Pn, Pn}, pc);  // bins 4k+3, 4k+2
+    if (k == 0) a01 = f2{Pc, Pc};                            // both indices clamp to plane 0
+    if (k == Dc - 1) a32 = f2{Pc, Pc};                       // both indices are Dc - 1: the tie rule
+    // arg-max: strictly larger only, in bin order, so the lowest bin of a tie stays
+    const int d0 = 4 * k;
+    float mn = m;
+    db = a01.x > mn ? d0 : db;     mn = fmaxf(mn, a01.x);
+    db = a01.y > mn ? d0 + 1 : db; mn = fmaxf(mn, a01.y);
+    db = a32.y > mn ? d0 + 2 : db; mn = fmaxf(mn, a32.y);
+    db = a32.x > mn ? d0 + 3 : db; mn = fmaxf(mn, a32.x);
+    if (mn > m) {                                            // rare after the first few planes
+      const float dm = m - mn;                               // -inf on the first plane: rs = 0, sums are 0
+      const float rs = __builtin_amdgcn_exp2f(LOG2E * dm);
+      t2 = (m == -INFINITY) ? f2{0.f, 0.f} : f2{rs, rs} * __builtin_elementwise_fma(f2{dm, dm}, l2, t2);
+      l2 *= f2{rs, rs}; s2 *= f2{rs, rs}; m = mn;
+    }
+    const f2 nm = {-m, -m};
+    const f2 u01 = a01 + nm, u32 = a32 + nm;
+    const f2 u23 = {u32.y, u32.x};
+    const f2 w01 = u01 * log2e, w23 = u23 * log2e;
+    const f2 e01 = {__builtin_amdgcn_exp2f(w01.x), __builtin_amdgcn_exp2f(w01.y)};
+    const f2 e23 = {__builtin_amdgcn_exp2f(w23.x), __builtin_amdgcn_exp2f(w23.y)};
+    l2 += e01; l2 += e23;
+    s2 = __builtin_elementwise_fma(d01, e01, s2);
+    s2 = __builtin_elementwise_fma(d23, e23, s2);
+    t2 = __builtin_elementwise_fma(e01, u01, t2);
+    t2 = __builtin_elementwise_fma(e23, u23, t2);
+    d01 += four; d23 += four;
+    Pm = Pc; Pc = Pn;
+  }
+  return Cf{m, l2.x + l2.y, s2.x + s2.y, t2.x + t2.y, db};
+}
+
+// Fine value of bin d from the pixel's planes (interpolating forms; the x4 head's weights are what
+// lerp_at gives for sd = 1/4, exactly).  (k, P0, P1) cache planes k and min(k + 1, Dc - 1).
+__device__ __forceinline__ float cf_fine(const SaParams& p, const float* __restrict__ base, long ps,
+                                         const Stencil& st, float sg, int d, int align, int& k, float& P0,
+                                         float& P1) {
+  const Lerp ld = lerp_at(d, p.sd, p.Dc, p.D, align);
+  if (ld.i0 != k) {
+    if (ld.i0 == k + 1) { P0 = P1; }
+    else { P0 = sg * cf_plane(base, ps, ld.i0, st); }
+    k = ld.i0;
+    P1 = sg * cf_plane(base, ps, min(k + 1, p.Dc - 1), st);
+  }
+  if (ld.i1 == ld.i0) return P0;                            // the tie rule
+  // the product with the larger weight is rounded, the other fused: the x4 form's a01 / a32, bit for bit,
+  // so pass B sees exp(0) at d* in every form
+  return ld.w1 >= ld.w0 ? fmaf(ld.w0, P0, ld.w1 * P1) : fmaf(ld.w1, P1, ld.w0 * P0);
+}
+
+// Merge, pass B and the stores.  `src`: the pixel's column of the (B,D,H,W) cost (no-upsample form);
+// `base` / `st`: the batch's coarse planes and the pixel's stencil (interpolating forms).
+template <bool UPSAMPLE, int DSPLIT>
+__device__ __forceinline__ void cf_finish(const CfParams& c, Cf acc, bool live, int seg, int x, int y, int b,
+                                          const float* __restrict__ src, const float* __restrict__ base,
+                                          const Stencil& st, float sg, int align) {
+  constexpr int PXW = DSM_WAVE / DSPLIT;
+  const SaParams& p = c.sa;
+#pragma unroll
+  for (int off = PXW; off < DSM_WAVE; off <<= 1) {
+    Cf o;
+    o.m = __shfl_xor(acc.m, off); o.l = __shfl_xor(acc.l, off); o.s = __shfl_xor(acc.s, off);
+    o.t = __shfl_xor(acc.t, off); o.db = __shfl_xor(acc.db, off);
+    acc = cf_merge(acc, o);
+  }
+  float pw = 0.f, sw = 0.f;
+  if (c.peak || c.pwin) {                                   // uniform
+    if (live) {
+      const int lo = max(0, acc.db - c.radius), hi = min(p.D - 1, acc.db + c.radius);
+      const int per = (hi - lo + DSPLIT) / DSPLIT;          // ceil((hi - lo + 1) / DSPLIT)
+      const int w_lo = lo + seg * per, w_hi = min(hi + 1, w_lo + per);
+      if (UPSAMPLE) {
+        const long ps = (long)p.Hc * p.Wc;
+        int k = -2; float P0 = 0.f, P1 = 0.f;
+        for (int d = w_lo; d < w_hi; ++d) {
+          const float e = __expf(cf_fine(p, base, ps, st, sg, d, align, k, P0, P1) - acc.m);
+          pw += e; sw = fmaf((float)d, e, sw);
+        }
+      } else {
+        const long ps = (long)p.H * p.W;
+        for (int d = w_lo; d < w_hi; ++d) {
+          const float e = __expf(sg * src[d * ps] - acc.m);
+          pw += e; sw = fmaf((float)d, e, sw);
+        }
+      }
+    }
+#pragma unroll
+    for (int off = PXW; off < DSM_WAVE; off <<= 1) {
+      pw += __shfl_xor(pw, off); sw += __shfl_xor(sw, off);
+    }
+  }
+  if (live && seg == 0) {
+    const long o = ((long)b * p.H + y) * p.W + x;
+    const float inv_l = 1.f / acc.l;
+    p.disp[o] = acc.s * inv_l;
+    if (c.pmax) c.pmax[o] = inv_l;                           // the arg-max term is exp(0)
+    if (c.pwin) c.pwin[o] = fminf(pw * inv_l, 1.f);
+    if (c.peak) c.peak[o] = sw / pw;
+    if (c.entropy)
+      c.entropy[o] = fminf(fmaxf(logf(acc.l) - acc.t * inv_l, 0.f), logf((float)p.D));
+  }
+}
+
+template <bool UPSAMPLE, int DSPLIT>
+__global__ __launch_bounds__(256) void disp_confidence_kernel(CfParams c) {
+  constexpr int PXW = DSM_WAVE / DSPLIT;
+  const SaParams& p = c.sa;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int seg = lane / PXW;
+  const int x = (blockIdx.x * 4 + wave) * PXW + (lane % PXW);
+  const int y = blockIdx.y, b = blockIdx.z;
+  const bool live = x < p.W;
+  const int dper = (p.D + DSPLIT - 1) / DSPLIT;
+  const int d_lo = seg * dper, d_hi = min(p.D, d_lo + dper);
+  const float sg = p.sign;
+  Cf acc = cf_neutral();
+  Stencil st = {};
+  const float* src = nullptr;
+  const float* base = nullptr;
+  if (live) {
+    if (UPSAMPLE) {
+      st = cf_stencil(p, y, x, p.align);
+      const long ps = (long)p.Hc * p.Wc;
+      base = p.cost + (long)b * p.Dc * ps;
+      int k = -2; float P0 = 0.f, P1 = 0.f;
+      for (int d = d_lo; d < d_hi; ++d) cf_push(acc, cf_fine(p, base, ps, st, sg, d, p.align, k, P0, P1), d);
+    } else {
+      const long ps = (long)p.H * p.W;
+      src = p.cost + (long)b * p.D * ps + (long)y * p.W + x;
+#pragma unroll 4
+      for (int d = d_lo; d < d_hi; ++d) cf_push(acc, sg * src[d * ps], d);
+    }
+  }
+  cf_finish<UPSAMPLE, DSPLIT>(c, acc, live, seg, x, y, b, src, base, st, sg, p.align);
+}
+
+template <int DSPLIT>
+__global__ __launch_bounds__(256) void disp_confidence_up4_kernel(CfParams c) {
+  constexpr int PXW = DSM_WAVE / DSPLIT;
+  const SaParams& p = c.sa;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int seg = lane / PXW;
+  const int x = (blockIdx.x * 4 + wave) * PXW + (lane % PXW);
+  const int y = blockIdx.y, b = blockIdx.z;
+  const bool live = x < p.W;
+  const int kper = (p.Dc + DSPLIT - 1) / DSPLIT;
+  const int k_lo = seg * kper, k_hi = min(p.Dc, k_lo + kper);
+  const float sg = p.sign;
+  Cf acc = cf_neutral();                                   // what a lane without planes contributes
+  Stencil st = {};
+  const float* base = nullptr;
+  if (live) {
+    st = cf_stencil(p, y, x, 0);
+    const long ps = (long)p.Hc * p.Wc;
+    base = p.cost + (long)b * p.Dc * ps;
+    if (k_lo < k_hi) {
+      acc = cf_up4_segment(base, ps, st, sg, k_lo, k_hi, p.Dc);
+    }
+  }
+  cf_finish<true, DSPLIT>(c, acc, live, seg, x, y, b, nullptr, base, st, sg, 0);
+}
+
+struct CfPlan { SaFwdPlan sa; int radius; };
+
+static int pick_conf(const void* cost, const void* disp, int B, int Dc, int Hc, int Wc, int D, int H, int W,
+                     int align_corners, int radius, int dtype, CfPlan* pl) {
+  int rc = pick_sa_fwd(cost, disp, B, Dc, Hc, Wc, D, H, W, align_corners, dtype, &pl->sa);
+  if (rc != DSM_OK) return rc;
+  DSM_REQUIRE(radius >= 0, DSM_ERR_ARG);
+  pl->radius = radius < D ? radius : D;        // r >= D - 1 is the whole range; keeps d* + r in an int
+  return DSM_OK;
+}
+
+extern "C" int dsm_disp_confidence_fwd_plan(const void* cost, const void* disp, const void* peak,
+                                            const void* pmax, const void* pwin, const void* entropy, int B,
+                                            int Dc, int Hc, int Wc, int D, int H, int W, int negate,
+                                            int align_corners, int radius, int dtype, char* buf, int len) {
+  (void)peak; (void)pmax; (void)pwin; (void)entropy; (void)negate;
+  DSM_REQUIRE(buf && len > 0, DSM_ERR_ARG);
+  CfPlan pl;
+  int rc = pick_conf(cost, disp, B, Dc, Hc, Wc, D, H, W, align_corners, radius, dtype, &pl);
+  if (rc != DSM_OK) return rc;
+  if (pl.sa.up4) snprintf(buf, (size_t)len, "conf_up4<%d>", pl.sa.ds);
+  else snprintf(buf, (size_t)len, "conf<%s,%d>", pl.sa.up ? "true" : "false", pl.sa.ds);
+  return DSM_OK;
+}
+
+extern "C" int dsm_disp_confidence_fwd(const void* cost, void* disp, void* peak, void* pmax, void* pwin,
+                                       void* entropy, int B, int Dc, int Hc, int Wc, int D, int H, int W,
+                                       int negate, int align_corners, int radius, int dtype,
+                                       dsm_stream_t stream) {
+  CfPlan pl;
+  int rc = pick_conf(cost, disp, B, Dc, Hc, Wc, D, H, W, align_corners, radius, dtype, &pl);
+  if (rc != DSM_OK) return rc;
+  CfParams c;
+  SaParams& p = c.sa;
+  p.cost = (const float*)cost; p.disp = (float*)disp; p.stats = nullptr;
+  p.Dc = Dc; p.Hc = Hc; p.Wc = Wc; p.D = D; p.H = H; p.W = W;
+  p.sd = src_scale(Dc, D, align_corners); p.sh = src_scale(Hc, H, align_corners);
+  p.sw = src_scale(Wc, W, align_corners);
+  p.sign = negate ? -1.f : 1.f; p.align = align_corners;
+  c.peak = (float*)peak; c.pmax = (float*)pmax; c.pwin = (float*)pwin; c.entropy = (float*)entropy;
+  c.radius = pl.radius;
+  const int ds = pl.sa.ds;
+  dim3 grid(dsm_cdiv(W, 4 * (DSM_WAVE / ds)), H, B), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  dsm_clear_stale_error();
+#define CF_LAUNCH(UP, DS) hipLaunchKernelGGL((disp_confidence_kernel<UP, DS>), grid, block, 0, s, c)
+  if (pl.sa.up4) {
+    DSM_REQUIRE(ds == 4, DSM_ERR_UNSUPPORTED);       // unreachable: see pick_sa_fwd
+    hipLaunchKernelGGL(disp_confidence_up4_kernel<4>, grid, block, 0, s, c);
+  } else if (pl.sa.up) { if (ds == 4) CF_LAUNCH(true, 4); else if (ds == 2) CF_LAUNCH(true, 2); else CF_LAUNCH(true, 1); }
+  else { if (ds == 4) CF_LAUNCH(false, 4); else if (ds == 2) CF_LAUNCH(false, 2); else CF_LAUNCH(false, 1); }
+#undef CF_LAUNCH
+  return dsm_launch_status();
+}
+
 // The adjoint dsm_soft_argmin_bwd launches: chosen here once, for the launch code and for
 // dsm_soft_argmin_bwd_plan.
 enum { SAB_DIRECT = 0, SAB_TILE = 1, SAB_FALLBACK = 2 };

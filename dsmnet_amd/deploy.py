@@ -155,6 +155,17 @@ def lr_predict(model, imgL_np, imgR_np, threshold=1.0, fill=False):
     return {k: (v[0, 0] if v.dim() == 4 else v[0]).cpu().numpy() for k, v in res.items()}
 
 
+def conf_predict(model, imgL_np, imgR_np, radius=4):
+    """``disp_predict`` with the cost head's confidence (``postprocess.predict_confidence``): the images go
+    through the same preparation; ``disp``, ``peak``, ``pmax``, ``pwin`` and ``entropy`` come back as (H,W)
+    numpy arrays."""
+    from .postprocess import predict_confidence
+    transform = Stereo_normalize()
+    prep = lambda im: transform(torch.from_numpy(im.copy().transpose(2, 0, 1)[None]).float().cuda() / 255.0)
+    res = predict_confidence(model, prep(imgL_np), prep(imgR_np), radius=radius)
+    return {k: (v[0, 0] if v.dim() == 4 else v[0]).cpu().numpy() for k, v in res.items()}
+
+
 def evaluate_consistent(imgL_np, imgR_np, disp, mask, path_disp_gt, flip=False):
     """``evaluate_pair`` over the consistent pixels only: the ground truth is zeroed (a hole) where ``mask``
     is false.  ``disp`` / ``mask`` / the file are the predicted view's, as for ``evaluate_pair``."""
@@ -194,6 +205,16 @@ def build_parser():
     ap.add_argument("--fill", action="store_true",
                     help="with --lr_check: write the disparity with the inconsistent pixels filled from "
                          "the background")
+    ap.add_argument("--confidence", action="store_true",
+                    help="psmnet / gcnet: write <stem>_conf.png next to the disparity, the probability mass of "
+                         "the window around the cost head's arg-max bin as 8-bit gray (white: confident)")
+    ap.add_argument("--peak", action="store_true",
+                    help="psmnet / gcnet: write the peak-window disparity (the regression over the window around "
+                         "the arg-max bin) in place of the expectation over the whole range")
+    ap.add_argument("--conf_radius", default=4, type=int, help="half-width of that window, in disparity bins")
+    ap.add_argument("--conf_threshold", default=None, type=float,
+                    help="with --confidence and --path_disp_gt: also print D1 / EPE over the pixels whose window "
+                         "mass is at least this, and their share")
     return ap
 
 
@@ -203,14 +224,32 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.fill and not args.lr_check:
         raise SystemExit("--fill needs --lr_check")
+    if args.peak and args.lr_check:
+        raise SystemExit("--peak cannot be combined with --lr_check: the check compares the two views' expectation maps")
+    if args.conf_threshold is not None and not args.confidence:
+        raise SystemExit("--conf_threshold needs --confidence")
+    if args.conf_radius < 0:
+        raise SystemExit("--conf_radius must be >= 0")
     if not torch.cuda.is_available():
         raise SystemExit("dsmnet_amd.deploy needs an MI355X: the HIP path has no CPU fallback")
     imgL, imgR = imread(args.path_left), imread(args.path_right)
     model = model_create_by_name(args.net, args.maxdisparity)
     load_weights(model, args.path_weight)
     model = model.eval().cuda()
-    mask = None
-    if args.lr_check:
+    mask = conf = None
+    if args.confidence or args.peak:
+        # one forward of the pair that predicts the written view (with --lr_check too: the check's own
+        # forwards are not touched); --flip mirrors and swaps, and the maps are flipped back
+        pair = (np.flip(imgR, axis=1), np.flip(imgL, axis=1)) if args.flip else (imgL, imgR)
+        try:
+            conf = conf_predict(model, pair[0], pair[1], args.conf_radius)
+        except TypeError as e:                   # a network without a cost head
+            raise SystemExit("--confidence / --peak: %s" % e)
+        if args.flip:
+            conf = {k: np.flip(v, axis=-1) for k, v in conf.items()}
+    if args.peak or (conf is not None and not args.lr_check):
+        disp, out = conf["peak" if args.peak else "disp"], args.out or "disp%s.png" % ("R" if args.flip else "L")
+    elif args.lr_check:
         side = "R" if args.flip else "L"
         res = lr_predict(model, imgL, imgR, args.lr_threshold, args.fill)
         raw, mask, out = res["disp" + side], res["mask" + side], args.out or "disp%s.png" % side
@@ -226,6 +265,12 @@ def main(argv=None):
         disp, out = disp_predict(model, imgL, imgR, True), args.out or "dispL.png"
     if args.path_disp_gt and mask is None:
         print("D1 %.4f %%  EPE %.4f px  pixelerror %.4f" % evaluate_pair(imgL, imgR, disp, args.path_disp_gt, args.flip))
+    if args.path_disp_gt and conf is not None and args.conf_threshold is not None:
+        sure = conf["pwin"] >= args.conf_threshold
+        scored = raw if args.lr_check else disp
+        print("confident pixels (pwin >= %g, %.2f %%): D1 %.4f %%  EPE %.4f px  pixelerror %.4f"
+              % ((args.conf_threshold, 100.0 * sure.mean()) +
+                 tuple(evaluate_consistent(imgL, imgR, scored, sure, args.path_disp_gt, args.flip))))
     if out.endswith(".pfm"):
         from .img_rw import save_pfm
         save_pfm(out, np.ascontiguousarray(disp, dtype=np.float32))
@@ -235,6 +280,11 @@ def main(argv=None):
     if mask is not None:
         import matplotlib.pyplot as plt
         plt.imsave(os.path.splitext(out)[0] + "_mask.png", mask.astype(np.uint8) * 255, cmap="gray", vmin=0, vmax=255)
+    if args.confidence:
+        from .img_rw import imwrite
+        gray = np.rint(np.clip(conf["pwin"], 0.0, 1.0) * 255.0).astype(np.uint8)
+        # the levels themselves, R = G = B (a colour map would quantise them a second time)
+        imwrite(os.path.splitext(out)[0] + "_conf.png", np.repeat(gray[:, :, None], 3, axis=2))
     return out
 
 

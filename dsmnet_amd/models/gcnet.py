@@ -103,7 +103,23 @@ class gcnet(nn.Module):
         with cv.amax_scope(imL.device):
             return self._forward(imL, imR, mode)
 
+    def head_cost(self, imL, imR):
+        """``(cost, out_size, negate, align_corners, crop)``: what the head (``l37``) hands to
+        ``costvolume.soft_argmin`` in ``forward`` -- for ``costvolume.soft_argmin_confidence``.  Eval mode;
+        ``crop = (H, W)``: the maps are cut to the images' size as ``forward`` cuts its own."""
+        if self.training:
+            raise RuntimeError("gcnet.head_cost: eval mode only (call model.eval() first)")
+        with cv.amax_scope(imL.device):
+            xL, virtual = self._volume(imL, imR)
+            cost = self.layer3d.cost(xL, virtual)
+        return cost, None, True, False, (imL.shape[-2], imL.shape[-1])
+
     def _forward(self, imL, imR, mode):
+        xL, virtual = self._volume(imL, imR)
+        oL = self.layer3d(xL, mode, virtual)[:, :, : imL.shape[-2], : imL.shape[-1]]
+        return [0], [oL]
+
+    def _volume(self, imL, imR):
         if imL.shape != imR.shape:
             raise ValueError("gcnet: imL and imR must have the same shape")   # gcnet.py:127
         self.__dict__["_both"] = None
@@ -114,8 +130,7 @@ class gcnet(nn.Module):
         if (both is not None and both.is_cuda and cv.get_option("fuse_volume") and
                 not torch.is_grad_enabled() and cv.virtual_volume_ok(both.shape[1])):
             virtual = cv.VirtualVolume(both, self.D, False)
-        oL = self.layer3d(xL, mode, virtual)[:, :, : imL.shape[-2], : imL.shape[-1]]
-        return [0], [oL]
+        return xL, virtual
 
 
 class gcnet_LR(nn.Module):

@@ -120,7 +120,24 @@ class PSMNet(nn.Module):
         with cv.amax_scope(left.device):
             return self._forward(left, right)
 
+    def head_cost(self, left, right):
+        """``(cost, out_size, negate, align_corners, crop)``: what the final head (``cost3``) hands to
+        ``costvolume.soft_argmin`` in ``forward`` -- for ``costvolume.soft_argmin_confidence``.  Eval mode;
+        ``crop`` is None (the head upsamples to the images' size)."""
+        if self.training:
+            raise RuntimeError("PSMNet.head_cost: eval mode only (call model.eval() first)")
+        with cv.amax_scope(left.device):
+            (_, _, cost3), size = self._head_costs(left, right)
+        return cost3, size, False, self.align_corners, None
+
     def _forward(self, left, right):
+        (cost1, cost2, cost3), size = self._head_costs(left, right)
+        pred1 = cv.soft_argmin(cost1, size, align_corners=self.align_corners)
+        pred2 = cv.soft_argmin(cost2, size, align_corners=self.align_corners)
+        pred3 = cv.soft_argmin(cost3, size, align_corners=self.align_corners)
+        return [0, 0, 0], [pred3, pred2, pred1]
+
+    def _head_costs(self, left, right):
         self.__dict__["_both"] = None
         refimg_fea, targetimg_fea = self.features(left, right)
         both = self.__dict__.pop("_both")
@@ -132,8 +149,4 @@ class PSMNet(nn.Module):
         else:
             cost = cv.concat_volume(refimg_fea, targetimg_fea, self.maxdisp // 4, mask_left=True)
         size = (self.maxdisp, left.shape[2], left.shape[3])
-        cost1, cost2, cost3 = self.regularise(cost)
-        pred1 = cv.soft_argmin(cost1, size, align_corners=self.align_corners)
-        pred2 = cv.soft_argmin(cost2, size, align_corners=self.align_corners)
-        pred3 = cv.soft_argmin(cost3, size, align_corners=self.align_corners)
-        return [0, 0, 0], [pred3, pred2, pred1]
+        return self.regularise(cost), size

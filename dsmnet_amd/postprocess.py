@@ -5,6 +5,10 @@ views and the background fill of the pixels it rejects (csrc/lrcheck.hip, ``cost
 The check is the one the ``-mask`` objectives train with (losses/loss.py:451-455: each view's map is
 compared with the other view's map warped by ``imwrap_BCHW(.., fliplr=True)``); the right view is
 predicted as ``deploy --flip`` does it, from the mirrored and swapped pair (stereo.py:142-150).
+
+``predict_confidence`` answers the same question from ONE forward of a cost-volume network: the softmax its
+head regresses from, read for its peak, the mass and the disparity of the window around it, and its entropy
+(csrc/soft_argmin.hip ``dsm_disp_confidence_fwd``, ``costvolume.soft_argmin_confidence``).
 """
 import torch
 
@@ -20,6 +24,35 @@ def _first_map(out):
 def _is_lr_pair(out):
     """``gcnet_LR``'s return convention: a pair of tensors ``(oL, oR)``, each in its own camera's frame."""
     return isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(t) for t in out)
+
+
+def predict_confidence(model, imL, imR, radius=4):
+    """The disparity of one batch with the confidence its cost head carries, from ONE forward:
+    ``costvolume.soft_argmin_confidence`` on what ``model.head_cost`` hands to the soft-argmin.
+
+    ``model``: a cost-volume network of the factory (``psmnet``, ``gcnet``).  Eval mode, no gradients.
+    Returns a dict of device tensors shaped like the network's first map ((B,H,W) for PSMNet, (B,1,H,W)
+    for GCNet, cropped as its ``forward`` crops): ``disp`` (the map ``forward`` returns), ``peak`` (the
+    regression over ``[d* - radius, d* + radius]`` around the arg-max bin, which does not average across
+    the modes at a depth edge), ``pmax``, ``pwin`` (the probability mass of that window: near 1 where the
+    distribution is unimodal) and ``entropy`` (nats).
+
+    ``dispnet``, ``dispnetcorr`` and ``iresnet`` regress disparity directly -- there is no distribution
+    over disparities to read a confidence from -- and are refused with a ``TypeError``."""
+    if not callable(getattr(model, "head_cost", None)):
+        raise TypeError("predict_confidence: %s regresses disparity directly and has no distribution over "
+                        "disparities (no head_cost); confidence maps exist for the cost-volume networks "
+                        "(psmnet, gcnet) only" % (getattr(model, "name", None) or type(model).__name__))
+    model.eval()
+    with torch.no_grad():
+        cost, out_size, negate, align_corners, crop = model.head_cost(imL, imR)
+        maps = cv.soft_argmin_confidence(cost, out_size, negate=negate, align_corners=align_corners, radius=radius)
+    res = {}
+    for name, t in zip(maps._fields, maps):
+        if crop is not None:                     # GCNet: (B,1,H,W), cut as its forward cuts
+            t = t.unsqueeze(1)[:, :, : crop[0], : crop[1]]
+        res[name] = t
+    return res
 
 
 def left_right_check(model, imL, imR, threshold=1.0, fill=True):

@@ -204,6 +204,28 @@ int dsm_soft_argmin_bwd_plan(const void* cost, const void* disp, const void* sta
                              int B, int Dc, int Hc, int Wc, int D, int H, int W,
                              int negate, int align_corners, int dtype, char* buf, int len);
 
+/* (ABI v7, additive) Confidence heads: the distribution dsm_soft_argmin_fwd regresses from, kept for
+ * four more per-pixel maps, in one launch.  Inputs as dsm_soft_argmin_fwd; with v_d the sign times the
+ * interpolated cost, p = softmax(v), d* the smallest d with v_d = max v and the window
+ * Wn = [max(0, d* - radius), min(D - 1, d* + radius)], all maps (B,H,W) fp32:
+ *   disp    = sum_d d p_d            (what dsm_soft_argmin_fwd writes)
+ *   pmax    = p_{d*}                   pwin = sum_{Wn} p_d
+ *   peak    = sum_{Wn} d p_d / pwin    (the regression restricted to the window around the arg-max)
+ *   entropy = -sum_d p_d ln p_d        (nats, in [0, ln D])
+ * Any of peak, pmax, pwin, entropy may be NULL and is then skipped; radius >= 0 (DSM_ERR_ARG otherwise),
+ * radius >= D - 1 gives pwin = 1 and peak = disp.  Wherever both interpolation indices along d coincide
+ * (the clamped top end) the fine value is the plane's own value, bit for bit, so the equal end bins of the
+ * D = 4 Dc head resolve to the lower one by rule, not by rounding.  Forward only; no host read, no
+ * allocation, capturable.  Plan: "conf_up4<4>", "conf<true,DS>", "conf<false,DS>", chosen as the
+ * soft-argmin forward's. */
+int dsm_disp_confidence_fwd(const void* cost, void* disp, void* peak, void* pmax, void* pwin, void* entropy,
+                            int B, int Dc, int Hc, int Wc, int D, int H, int W,
+                            int negate, int align_corners, int radius, int dtype, dsm_stream_t stream);
+int dsm_disp_confidence_fwd_plan(const void* cost, const void* disp, const void* peak, const void* pmax,
+                                 const void* pwin, const void* entropy,
+                                 int B, int Dc, int Hc, int Wc, int D, int H, int W,
+                                 int negate, int align_corners, int radius, int dtype, char* buf, int len);
+
 /* ---------------------------------------------------------------------------
  * (a4,a5) 3-D convolution block, k = 3, fused epilogue.  Replaces
  *   convbn_3d (+ReLU, +skip)            models/psmnet/submodule.py:16-19,
