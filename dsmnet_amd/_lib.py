@@ -111,6 +111,17 @@ class LrcheckArgs(ctypes.Structure):
 DSM_LRCHECK_OTHER_RIGHT_FRAME = 1
 
 
+class EncodeArgs(ctypes.Structure):
+    """struct dsm_encode_args (include/dsmnet_hip.h), 104 bytes."""
+    _fields_ = [("disp", c_void_p), ("gt", c_void_p), ("mask", c_void_p), ("u16", c_void_p), ("u8", c_void_p),
+                ("rgb", c_void_p), ("err", c_void_p), ("workspace", c_void_p), ("B", c_int), ("Hs", c_int),
+                ("Ws", c_int), ("y0", c_int), ("x0", c_int), ("h", c_int), ("w", c_int),
+                ("vmin", ctypes.c_float), ("vmax", ctypes.c_float), ("flags", c_int)]
+
+
+DSM_ENCODE_FLIP, DSM_ENCODE_AUTO_RANGE = 1, 2
+
+
 class ColorRecord(ctypes.Structure):
     """struct dsm_color_record (include/dsmnet_hip.h)."""
     _fields_ = [("order", c_int * 4), ("jitter", ctypes.c_float * 4), ("flags", c_int), ("alpha_row", c_int)]
@@ -209,6 +220,8 @@ SIGNATURES = {
     "dsm_lr_check": (c_int, [ctypes.POINTER(LrcheckArgs), c_void_p]),
     "dsm_fill_background_workspace_bytes": (c_size_t, [c_int] * 3),
     "dsm_fill_background": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
+    "dsm_disp_encode_workspace_bytes": (c_size_t, [c_int] * 3),
+    "dsm_disp_encode": (c_int, [ctypes.POINTER(EncodeArgs), c_void_p]),
     "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),
     "dsm_stereo_spatial": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SpatialRecord)] + [c_int] * 8 + [c_void_p]),
     "dsm_stereo_spatial_raw": (c_int, [c_void_p, c_size_t, ctypes.POINTER(FrameSource), c_void_p,

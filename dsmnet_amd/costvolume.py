@@ -2533,3 +2533,76 @@ def fill_background(disp, mask):
         rc = lib.dsm_fill_background(_p(d), _p(m), _p(out), _p(ws), B, H, W, _stream())
     _lib.check(rc, "dsm_fill_background")
     return out
+
+
+# ----------------------------------------------------------------------------
+# Result maps of a predicted map: KITTI 16-bit, 8-bit, viridis, error picture (csrc/encode.hip)
+# ----------------------------------------------------------------------------
+ENCODE_OUTPUTS = ("u16", "u8", "rgb", "err")
+
+
+def encode_disparity(disp, gt=None, mask=None, window=None, flip=False, want=("u16",), vrange=None):
+    """The bytes of the files a disparity map is kept in, in one launch and without a host read
+    (csrc/encode.hip, ``dsm_disp_encode``; the rules per output are in include/dsmnet_hip.h):
+
+        u16   (B,h,w) ``torch.uint16``: KITTI's encoding, ``rint(d * 256)`` in [1, 65535], 0 = invalid
+        u8    (B,h,w) ``torch.uint8``: ``clip(rint(d), 0, 255)``, what the reference's ``submit()`` writes
+        rgb   (B,h,w,3) ``torch.uint8``: viridis over ``vrange = (lo, hi)``; ``vrange=None`` is
+              ``plt.imsave``'s rule, each image over its own finite, unmasked range (one more launch)
+        err   (B,h,w,3) ``torch.uint8``: the KITTI devkit's log-scale error picture; needs ``gt``
+
+    ``disp``: (B,1,H,W) or PSMNet's (B,H,W), float32; ``gt`` the same shape, holes <= 0; ``mask`` the same
+    shape, ``torch.bool`` or ``torch.uint8``: a pixel it rejects (or whose ``disp`` is not finite) is 0 in
+    every output.  ``window = (y0, x0, h, w)``: the part of the frame that is written (default: all of
+    it) -- how padding added before the forward is cut off.  ``flip=True`` writes the window mirrored
+    (a right view predicted from the mirrored, swapped pair), bit-identical to encoding the flipped
+    tensors.  ``want``: a non-empty subset of ``ENCODE_OUTPUTS``.
+
+    Returns a dict of new device tensors.  No autograd; capturable: torch allocates, nothing synchronises."""
+    _require_device("encode_disparity", disp, gt)
+    names = tuple(want)
+    if not names or any(n not in ENCODE_OUTPUTS for n in names) or len(set(names)) != len(names):
+        raise ValueError("encode_disparity: want is a non-empty subset of %s, got %r" % (ENCODE_OUTPUTS, want))
+    if "err" in names and gt is None:
+        raise ValueError("encode_disparity: the error picture needs gt")
+    if mask is not None:
+        if not mask.is_cuda:
+            _require_device("encode_disparity", mask)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("encode_disparity: mask is torch.bool or torch.uint8, got %s" % (mask.dtype,))
+    maps, (B, Hs, Ws) = _plane_maps("encode_disparity", *[t for t in (disp, gt, mask) if t is not None])
+    d = maps[0]
+    g = maps[1] if gt is not None else None
+    m = maps[-1] if mask is not None else None
+    y0, x0, h, w = (0, 0, Hs, Ws) if window is None else [int(v) for v in window]
+    if min(h, w) < 1 or y0 < 0 or x0 < 0 or y0 + h > Hs or x0 + w > Ws:
+        raise ValueError("encode_disparity: window %r leaves the %dx%d frame" % (tuple(window), Hs, Ws))
+    a = _lib.EncodeArgs()
+    a.flags = _lib.DSM_ENCODE_FLIP if flip else 0
+    if "rgb" in names:
+        if vrange is None:
+            a.flags |= _lib.DSM_ENCODE_AUTO_RANGE
+        else:
+            a.vmin, a.vmax = float(vrange[0]), float(vrange[1])
+            if not (abs(a.vmin) <= 3.402823466e38 and abs(a.vmax) <= 3.402823466e38 and a.vmax >= a.vmin):
+                raise ValueError("encode_disparity: vrange is finite (in float32) with lo <= hi, got %r" % (vrange,))
+    lib = _lib.load()
+    dev = disp.device
+    shapes = {"u16": ((B, h, w), torch.uint16), "u8": ((B, h, w), torch.uint8),
+              "rgb": ((B, h, w, 3), torch.uint8), "err": ((B, h, w, 3), torch.uint8)}
+    out = {n: torch.empty(shapes[n][0], device=dev, dtype=shapes[n][1]) for n in names}
+    ws = None
+    if a.flags & _lib.DSM_ENCODE_AUTO_RANGE:
+        ws = torch.empty(lib.dsm_disp_encode_workspace_bytes(B, h, w) // 4, device=dev, dtype=torch.float32)
+        a.workspace = ws.data_ptr()
+    a.disp, a.gt, a.mask = d.data_ptr(), None if g is None else g.data_ptr(), None if m is None else m.data_ptr()
+    for n in names:
+        setattr(a, n, out[n].data_ptr())
+    a.B, a.Hs, a.Ws, a.y0, a.x0, a.h, a.w = B, Hs, Ws, y0, x0, h, w
+    per = {"u16": 2.0, "u8": 1.0, "rgb": 3.0, "err": 3.0}
+    work = B * h * w * (4.0 + (4.0 if "err" in names else 0.0) + (1.0 if m is not None else 0.0) +
+                        sum(per[n] for n in names) + ((4.0 + (1.0 if m is not None else 0.0)) if ws is not None else 0.0))
+    with torch.cuda.device(dev), _timed("encode_range+rows" if ws is not None else "encode_rows", work):
+        rc = lib.dsm_disp_encode(ctypes.byref(a), _stream())
+    _lib.check(rc, "dsm_disp_encode")
+    return out

@@ -215,7 +215,41 @@ def build_parser():
     ap.add_argument("--conf_threshold", default=None, type=float,
                     help="with --confidence and --path_disp_gt: also print D1 / EPE over the pixels whose window "
                          "mass is at least this, and their share")
+    ap.add_argument("--encode", default=None, choices=("kitti16", "u8", "viridis"),
+                    help="write the disparity PNG from the device encoder (costvolume.encode_disparity): kitti16 = "
+                         "16-bit value * 256 with 0 invalid (with --lr_check the inconsistent pixels), u8 = "
+                         "clip(rint(d), 0, 255), viridis = colours over --vrange (default: the map's own range)")
+    ap.add_argument("--vrange", nargs=2, type=float, default=None, metavar=("LO", "HI"),
+                    help="with --encode viridis: the fixed range of the colour map, so that frames compare")
+    ap.add_argument("--error_map", action="store_true",
+                    help="with --path_disp_gt: write <stem>_err.png next to the disparity, the KITTI devkit's "
+                         "log-scale error picture")
     return ap
+
+
+def encode_outputs(disp, out, encode=None, vrange=None, mask=None, path_disp_gt=None, error_map=False):
+    """The files of ``--encode`` / ``--error_map``: ``disp`` (H,W) float32 (and ``mask`` (H,W) bool, the ground
+    truth file) go to the device, ``costvolume.encode_disparity`` makes the bytes, ``submit.write_png``
+    writes ``out`` and ``<stem>_err.png``.  Returns the paths written."""
+    from . import costvolume as cv
+    from .submit import write_png
+    dev = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a, dtype=dtype))[None].cuda()
+    want = {"kitti16": "u16", "u8": "u8", "viridis": "rgb", None: None}[encode]
+    gt = None
+    if error_map:
+        from .img_rw import load_disp
+        gt = np.asarray(load_disp(path_disp_gt), dtype=np.float32)
+        if gt.shape != disp.shape:
+            raise ValueError("ground truth %s does not match the prediction %s" % (gt.shape, disp.shape))
+    res = cv.encode_disparity(dev(disp, np.float32), gt=None if gt is None else dev(gt, np.float32),
+                              mask=None if mask is None else dev(mask, np.uint8),
+                              want=tuple(n for n in (want, "err" if error_map else None) if n), vrange=vrange)
+    paths = []
+    for name, path in ((want, out), ("err" if error_map else None, os.path.splitext(out)[0] + "_err.png")):
+        if name:
+            write_png(path, res[name][0].cpu().numpy())
+            paths.append(path)
+    return paths
 
 
 def main(argv=None):
@@ -230,6 +264,12 @@ def main(argv=None):
         raise SystemExit("--conf_threshold needs --confidence")
     if args.conf_radius < 0:
         raise SystemExit("--conf_radius must be >= 0")
+    if args.vrange is not None and args.encode != "viridis":
+        raise SystemExit("--vrange needs --encode viridis")
+    if args.error_map and not args.path_disp_gt:
+        raise SystemExit("--error_map needs --path_disp_gt")
+    if args.encode and (args.out or "").endswith(".pfm"):
+        raise SystemExit("--encode writes a PNG, --out names a PFM")
     if not torch.cuda.is_available():
         raise SystemExit("dsmnet_amd.deploy needs an MI355X: the HIP path has no CPU fallback")
     imgL, imgR = imread(args.path_left), imread(args.path_right)
@@ -271,7 +311,13 @@ def main(argv=None):
         print("confident pixels (pwin >= %g, %.2f %%): D1 %.4f %%  EPE %.4f px  pixelerror %.4f"
               % ((args.conf_threshold, 100.0 * sure.mean()) +
                  tuple(evaluate_consistent(imgL, imgR, scored, sure, args.path_disp_gt, args.flip))))
-    if out.endswith(".pfm"):
+    if args.encode or args.error_map:
+        # kitti16 / u8 mark what the check rejects as invalid; a filled map has no such pixel
+        encode_outputs(disp, out, args.encode, args.vrange, None if args.fill else mask, args.path_disp_gt,
+                       args.error_map)
+    if args.encode:
+        pass
+    elif out.endswith(".pfm"):
         from .img_rw import save_pfm
         save_pfm(out, np.ascontiguousarray(disp, dtype=np.float32))
     else:

@@ -829,6 +829,62 @@ size_t dsm_fill_background_workspace_bytes(int B, int H, int W);
 int dsm_fill_background(const void* disp, const void* mask, void* out, void* workspace, int B, int H, int W,
                         dsm_stream_t stream);
 
+/* (ABI v7, additive) Result maps of a disparity map (csrc/encode.hip), the inverse of dsm_stereo_spatial_raw:
+ * from the fp32 map to the bytes of the files a user keeps.  One launch; two with DSM_ENCODE_AUTO_RANGE.  No
+ * atomics, no host synchronisation, capturable.
+ * Inputs, all in one source frame and read at the same element: disp (B,Hs,Ws) fp32 contiguous (a
+ * (B,1,Hs,Ws) map is the same memory); gt (B,Hs,Ws) fp32 or NULL, holes <= 0; mask (B,Hs,Ws) uint8 or NULL,
+ * non-zero = valid.
+ * Window: output pixel (y, x), 0 <= y < h, 0 <= x < w, reads source pixel (y0 + y, x0 + x) -- how padding
+ * added before the forward is cut off.  With DSM_ENCODE_FLIP output column x reads source column
+ * x0 + w - 1 - x (a right view predicted from the mirrored, swapped pair): no copy, bit-identical to
+ * encoding the flipped tensors.
+ * Outputs, dense, each may be NULL, not all four.  d is the prediction, every operation fp32:
+ *    u16  (B,h,w) uint16, KITTI's encoding: q = rintf(d * 256.0f) (ties to even) clamped to [1, 65535];
+ *         0 where d is not finite or mask is 0.  A finite d <= 0 gives 1: a submission is dense.
+ *    u8   (B,h,w) uint8, what stereo.py:174 writes (cv2.imwrite of a float plane = convertTo(CV_8U)):
+ *         rintf(d) clamped to [0, 255]; NaN and masked pixels 0, +Inf 255, -Inf 0.
+ *    rgb  (B,h,w,3) uint8, viridis (matplotlib's table as bytes, csrc/viridis_lut.hpp):
+ *         v = ((d - lo) / (hi - lo)) * 256.0f, entry (int)v; v < 0 gives entry 0, v >= 256 entry 255,
+ *         hi == lo entry 0 everywhere (as does a v that is NaN because the range overflows fp32);
+ *         non-finite or masked pixels (0,0,0).  lo, hi = vmin, vmax, or with DSM_ENCODE_AUTO_RANGE, per
+ *         image, the minimum and maximum over the finite, unmasked pixels inside the window (plt.imsave's
+ *         rule; an image without such a pixel is all black).  Auto-range costs one more launch, which writes
+ *         per-block extremes to `workspace` (dsm_disp_encode_workspace_bytes(B, h, w) bytes, 0 for
+ *         non-positive sizes); the encode launch reduces them itself.
+ *    err  (B,h,w,3) uint8, needs gt: the KITTI devkit's log-scale error picture, undilated.  Scored where gt is
+ *         finite and > 0 and mask allows it, every other pixel (0,0,0).  e = fabsf(gt - d),
+ *         n = fminf(e / 3.0f, (e / gt) / 0.05f); the colour of the bin lo <= n < hi:
+ *           [0,1/16) 49,54,149  [1/16,1/8) 69,117,180  [1/8,1/4) 116,173,209  [1/4,1/2) 171,217,233
+ *           [1/2,1) 224,243,248  [1,2) 254,224,144  [2,4) 253,174,97  [4,8) 244,109,67  [8,16) 215,48,39
+ *           [16,inf) 165,0,38, which a non-finite d on a scored pixel takes too.  The step at n = 1 is D1's.
+ * DSM_ERR_ARG (nothing launched): NULL args or disp; all four outputs NULL; err without gt; auto-range rgb
+ * without a workspace; a non-positive B, Hs, Ws, h or w; a window that leaves the frame (y0 or x0 < 0,
+ * y0 + h > Hs, x0 + w > Ws); with rgb and a fixed range, vmin or vmax not finite or vmax < vmin; any other
+ * flags bit; an output (or the workspace in use) overlapping an input, or an output overlapping that workspace.
+ * DSM_ERR_ALIGN: disp, gt or the workspace in use not 4-byte aligned, u16 not 2-byte aligned.
+ * DSM_ERR_UNSUPPORTED: B * Hs * Ws >= 2^31 (the kernel's 32-bit element indices).
+ * sizeof(dsm_encode_args) == 104. */
+#define DSM_ENCODE_FLIP 1
+#define DSM_ENCODE_AUTO_RANGE 2
+typedef struct dsm_encode_args {
+  const void* disp;
+  const void* gt;
+  const void* mask;
+  void* u16;
+  void* u8;
+  void* rgb;
+  void* err;
+  void* workspace;
+  int B, Hs, Ws;
+  int y0, x0, h, w;
+  float vmin, vmax;
+  int flags;
+} dsm_encode_args;
+
+size_t dsm_disp_encode_workspace_bytes(int B, int h, int w);
+int dsm_disp_encode(const dsm_encode_args* args, dsm_stream_t stream);
+
 /* (ABI v7, additive) Stereo colour augmentation of a training batch, fused -- replaces
  * myTransforms/__init__.py:109-135 Stereo_color / Stereo_normalize applied by Stereo_color_batch,
  * i.e. myTransforms/aug_color.py ColorJitter (RandomOrder :175-203 over Brightness, Contrast,
