@@ -111,6 +111,13 @@ class LrcheckArgs(ctypes.Structure):
 DSM_LRCHECK_OTHER_RIGHT_FRAME = 1
 
 
+class SpeckleArgs(ctypes.Structure):
+    """struct dsm_speckle_args (include/dsmnet_hip.h), 80 bytes."""
+    _fields_ = [("disp", c_void_p), ("valid", c_void_p), ("out", c_void_p), ("keep", c_void_p),
+                ("size", c_void_p), ("workspace", c_void_p), ("B", c_int), ("H", c_int), ("W", c_int),
+                ("max_size", c_int), ("max_diff", ctypes.c_float), ("new_val", ctypes.c_float), ("flags", c_int)]
+
+
 class EncodeArgs(ctypes.Structure):
     """struct dsm_encode_args (include/dsmnet_hip.h), 104 bytes."""
     _fields_ = [("disp", c_void_p), ("gt", c_void_p), ("mask", c_void_p), ("u16", c_void_p), ("u8", c_void_p),
@@ -220,6 +227,8 @@ SIGNATURES = {
     "dsm_lr_check": (c_int, [ctypes.POINTER(LrcheckArgs), c_void_p]),
     "dsm_fill_background_workspace_bytes": (c_size_t, [c_int] * 3),
     "dsm_fill_background": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
+    "dsm_speckle_workspace_bytes": (c_size_t, [c_int] * 3),
+    "dsm_speckle_filter": (c_int, [ctypes.POINTER(SpeckleArgs), c_void_p]),
     "dsm_disp_encode_workspace_bytes": (c_size_t, [c_int] * 3),
     "dsm_disp_encode": (c_int, [ctypes.POINTER(EncodeArgs), c_void_p]),
     "dsm_stereo_color": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ColorRecord)] + [c_int] * 6 + [c_void_p]),

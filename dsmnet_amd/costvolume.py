@@ -16,6 +16,7 @@ Reference code each op replaces (sunshinnnn/DSMnet):
   supervised_pyramid_loss   losses/loss.py:326-338, 407-421, stereo.py:103-113
   stereo_metrics  utils/evaluate.py:9-73, stereo.py:103-113, utils/imwrap.py:37-72
   lr_check        utils/imwrap.py:37-72 (fliplr=True), losses/loss.py:393-404, 451-452
+  filter_speckles  beyond the reference: OpenCV's filterSpeckles (connected regions, the small ones removed)
   soft_argmin_confidence   the softmax of the two soft_argmin sites above, kept for its peak, window and entropy
 """
 import collections
@@ -2533,6 +2534,73 @@ def fill_background(disp, mask):
         rc = lib.dsm_fill_background(_p(d), _p(m), _p(out), _p(ws), B, H, W, _stream())
     _lib.check(rc, "dsm_fill_background")
     return out
+
+
+# ----------------------------------------------------------------------------
+# Speckle filter of a predicted map: connected regions, the small ones removed (csrc/speckle.hip)
+# ----------------------------------------------------------------------------
+Speckle = collections.namedtuple("Speckle", ("out", "keep", "size"))
+
+
+def filter_speckles(disp, max_size, max_diff, valid=None, new_val=0.0, want=("out", "keep")):
+    """The connected regions of ``disp`` with the small ones removed, on the device and without a host
+    read (csrc/speckle.hip, ``dsm_speckle_filter``): OpenCV's ``filterSpeckles(img, newVal,
+    maxSpeckleSize, maxDiff)``, StereoSGBM's ``speckleWindowSize`` / ``speckleRange``.  Exact:
+
+        node    a pixel with ``isfinite(disp)`` that ``valid`` (if given) allows; the value of any other
+                pixel is never used, so a NaN there cannot spread
+        edge    two 4-neighbours of one image, both nodes, with ``fabsf(disp[p] - disp[q]) <= max_diff``
+                in float32; images of a batch are never joined
+        region  a connected component (transitive: a ramp of steps <= ``max_diff`` is one region)
+        size    ``torch.int32``: the nodes of the pixel's region, 0 where the pixel is no node
+        keep    ``torch.bool``: node and ``size > max_size`` -- a region is a speckle iff
+                ``size <= max_size``; ``max_size = 0`` removes nothing but the pixels that are no nodes
+        out     ``disp`` where ``keep``, else ``new_val``
+
+    ``disp``: (B,1,H,W) or PSMNet's (B,H,W), float32, any H, W >= 1; ``valid`` the same shape,
+    ``torch.bool`` or ``torch.uint8`` (``lr_check``'s mask).  ``max_size``: int >= 0; ``max_diff``: finite
+    float >= 0.  ``want``: the entries to compute; the others are None.  Returns a ``Speckle`` of new
+    tensors of ``disp``'s shape.  Integer atomics only: two runs give the same bits.
+
+    No autograd backward: the inputs are detached.  Capturable: torch allocates (the workspace, 8 bytes per
+    pixel, is written before it is read in every call), nothing synchronises, the launches are one chain."""
+    names = tuple(want)
+    if not names or any(n not in Speckle._fields for n in names) or len(set(names)) != len(names):
+        raise ValueError("filter_speckles: want is a non-empty subset of %s, got %r" % (Speckle._fields, want))
+    if isinstance(max_size, bool) or int(max_size) != max_size or max_size < 0 or max_size >= 2 ** 31:
+        raise ValueError("filter_speckles: max_size is an int >= 0, got %r" % (max_size,))
+    if not (0.0 <= float(max_diff) <= 3.402823466e38):
+        raise ValueError("filter_speckles: max_diff is finite (in float32) and >= 0, got %r" % (max_diff,))
+    if valid is not None:
+        if valid.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("filter_speckles: valid is torch.bool or torch.uint8, got %s" % (valid.dtype,))
+        if valid.shape != disp.shape:
+            raise ValueError("filter_speckles: valid %s does not match disp %s" % (tuple(valid.shape), tuple(disp.shape)))
+    _require_device("filter_speckles", disp)
+    if valid is not None and not valid.is_cuda:
+        _require_device("filter_speckles", valid)
+    maps, (B, H, W) = _plane_maps("filter_speckles", *[t for t in (disp, valid) if t is not None])
+    if B * H * W >= 2 ** 31:
+        raise ValueError("filter_speckles: %d pixels are past the kernels' int32 indices" % (B * H * W))
+    lib = _lib.load()
+    dtypes = {"out": torch.float32, "keep": torch.uint8, "size": torch.int32}
+    out = {n: torch.empty(disp.shape, device=disp.device, dtype=dtypes[n]) for n in names}
+    ws = torch.empty(lib.dsm_speckle_workspace_bytes(B, H, W) // 4, device=disp.device, dtype=torch.int32)
+    a = _lib.SpeckleArgs()
+    a.disp, a.valid = maps[0].data_ptr(), None if valid is None else maps[1].data_ptr()
+    for n in names:
+        setattr(a, n, out[n].data_ptr())
+    a.workspace = ws.data_ptr()
+    a.B, a.H, a.W = B, H, W
+    a.max_size, a.max_diff, a.new_val, a.flags = int(max_size), float(max_diff), float(new_val), 0
+    work = B * H * W * (4.0 + (1.0 if valid is not None else 0.0) + 4 * 8.0 +
+                        sum(1.0 if n == "keep" else 4.0 for n in names))
+    with torch.cuda.device(disp.device), _timed("speckle_label_tiles+merge_borders+flatten_count+apply", work):
+        rc = lib.dsm_speckle_filter(ctypes.byref(a), _stream())
+    _lib.check(rc, "dsm_speckle_filter")
+    if "keep" in out:
+        out["keep"] = out["keep"].view(torch.bool)          # the kernel writes 0 / 1
+    return Speckle(*[out.get(n) for n in Speckle._fields])
 
 
 # ----------------------------------------------------------------------------

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["abi.hip", "corr1d.hip", "cost_volume.hip", "soft_argmin.hip", "conv3d.hip", "conv_f16.hip",
            "conv3d_bwd.hip", "bn3d.hip", "decoder.hip", "spp.hip", "warp.hip",
            "selfsup.hip", "color.hip", "spatial.hip", "frames.hip", "sepvol.hip", "suploss.hip", "relu_bwd.hip",
-           "metrics.hip", "lrcheck.hip", "encode.hip"]
+           "metrics.hip", "lrcheck.hip", "encode.hip", "speckle.hip"]
 LIB = os.path.join(HERE, "libdsmnet_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

@@ -145,14 +145,36 @@ def evaluate_pair(imgL_np, imgR_np, disp, path_disp_gt, flip=False):
                     np.ascontiguousarray(gt)[None, None])
 
 
-def lr_predict(model, imgL_np, imgR_np, threshold=1.0, fill=False):
+def lr_predict(model, imgL_np, imgR_np, threshold=1.0, fill=False, speckle=None):
     """``disp_predict`` of both views with the left-right check (``postprocess.left_right_check``): the
-    images go through the same preparation; the dict's (H,W) maps come back as numpy arrays, masks as bool."""
+    images go through the same preparation; the dict's (H,W) maps come back as numpy arrays, masks as bool.
+    ``speckle=(max_size, max_diff)``: as there (``keepL`` / ``keepR``, the fill from ``keep``)."""
     from .postprocess import left_right_check
     transform = Stereo_normalize()
     prep = lambda im: transform(torch.from_numpy(im.copy().transpose(2, 0, 1)[None]).float().cuda() / 255.0)
-    res = left_right_check(model, prep(imgL_np), prep(imgR_np), threshold=threshold, fill=fill)
+    res = left_right_check(model, prep(imgL_np), prep(imgR_np), threshold=threshold, fill=fill, speckle=speckle)
     return {k: (v[0, 0] if v.dim() == 4 else v[0]).cpu().numpy() for k, v in res.items()}
+
+
+def speckle_filter(disp, max_size, max_diff):
+    """An (H,W) float32 map through ``postprocess.remove_speckles`` on the device: ``(out, keep)`` as numpy
+    arrays, ``out`` with the removed (and the non-finite) pixels 0, ``keep`` bool."""
+    from .postprocess import remove_speckles
+    d = torch.from_numpy(np.ascontiguousarray(disp, dtype=np.float32))[None].cuda()
+    out, keep = remove_speckles(d, max_size, max_diff)
+    return out[0].cpu().numpy(), keep[0].cpu().numpy()
+
+
+def speckle_args(pair):
+    """``--speckle SIZE DIFF`` as ``(int, float)`` or None; ``SystemExit`` for values the filter refuses."""
+    if pair is None:
+        return None
+    size, diff = pair
+    if not (size >= 0 and size == int(size) and size < 2 ** 31):
+        raise SystemExit("--speckle SIZE is a whole number of pixels >= 0, got %r" % (size,))
+    if not (0.0 <= diff <= 3.402823466e38):
+        raise SystemExit("--speckle DIFF is a finite disparity difference >= 0, got %r" % (diff,))
+    return int(size), float(diff)
 
 
 def conf_predict(model, imgL_np, imgR_np, radius=4):
@@ -205,6 +227,14 @@ def build_parser():
     ap.add_argument("--fill", action="store_true",
                     help="with --lr_check: write the disparity with the inconsistent pixels filled from "
                          "the background")
+    ap.add_argument("--speckle", nargs=2, type=float, default=None, metavar=("SIZE", "DIFF"),
+                    help="remove the connected regions of at most SIZE pixels, neighbours being joined where they "
+                         "differ by at most DIFF (OpenCV's filterSpeckles; costvolume.filter_speckles).  With "
+                         "--lr_check: among the consistent pixels, and --fill, --encode, the mask picture and the "
+                         "consistent-pixel scores use what is kept.  Without: the written map is filtered alone, "
+                         "the removed pixels are 0 (invalid for --encode).  With --peak, or --confidence without "
+                         "--lr_check, it is that forward's written map that is filtered; the confidence picture "
+                         "and --conf_threshold's scores are never filtered")
     ap.add_argument("--confidence", action="store_true",
                     help="psmnet / gcnet: write <stem>_conf.png next to the disparity, the probability mass of "
                          "the window around the cost head's arg-max bin as 8-bit gray (white: confident)")
@@ -270,13 +300,14 @@ def main(argv=None):
         raise SystemExit("--error_map needs --path_disp_gt")
     if args.encode and (args.out or "").endswith(".pfm"):
         raise SystemExit("--encode writes a PNG, --out names a PFM")
+    speckle = speckle_args(args.speckle)
     if not torch.cuda.is_available():
         raise SystemExit("dsmnet_amd.deploy needs an MI355X: the HIP path has no CPU fallback")
     imgL, imgR = imread(args.path_left), imread(args.path_right)
     model = model_create_by_name(args.net, args.maxdisparity)
     load_weights(model, args.path_weight)
     model = model.eval().cuda()
-    mask = conf = None
+    mask = conf = keep = None
     if args.confidence or args.peak:
         # one forward of the pair that predicts the written view (with --lr_check too: the check's own
         # forwards are not touched); --flip mirrors and swaps, and the maps are flipped back
@@ -291,8 +322,9 @@ def main(argv=None):
         disp, out = conf["peak" if args.peak else "disp"], args.out or "disp%s.png" % ("R" if args.flip else "L")
     elif args.lr_check:
         side = "R" if args.flip else "L"
-        res = lr_predict(model, imgL, imgR, args.lr_threshold, args.fill)
-        raw, mask, out = res["disp" + side], res["mask" + side], args.out or "disp%s.png" % side
+        res = lr_predict(model, imgL, imgR, args.lr_threshold, args.fill, speckle)
+        raw, out = res["disp" + side], args.out or "disp%s.png" % side
+        mask = res[("keep" if speckle else "mask") + side]
         disp = res["filled" + side] if args.fill else raw
         if args.path_disp_gt:
             print("D1 %.4f %%  EPE %.4f px  pixelerror %.4f" % evaluate_pair(imgL, imgR, raw, args.path_disp_gt, args.flip))
@@ -305,16 +337,22 @@ def main(argv=None):
         disp, out = disp_predict(model, imgL, imgR, True), args.out or "dispL.png"
     if args.path_disp_gt and mask is None:
         print("D1 %.4f %%  EPE %.4f px  pixelerror %.4f" % evaluate_pair(imgL, imgR, disp, args.path_disp_gt, args.flip))
+    if speckle and not args.lr_check:
+        raw = disp
+        disp, keep = speckle_filter(raw, *speckle)
+        if args.path_disp_gt:
+            print("kept pixels (%.2f %%): D1 %.4f %%  EPE %.4f px  pixelerror %.4f"
+                  % ((100.0 * keep.mean(),) + tuple(evaluate_consistent(imgL, imgR, raw, keep, args.path_disp_gt, args.flip))))
     if args.path_disp_gt and conf is not None and args.conf_threshold is not None:
         sure = conf["pwin"] >= args.conf_threshold
-        scored = raw if args.lr_check else disp
+        scored = raw if (args.lr_check or speckle) else disp
         print("confident pixels (pwin >= %g, %.2f %%): D1 %.4f %%  EPE %.4f px  pixelerror %.4f"
               % ((args.conf_threshold, 100.0 * sure.mean()) +
                  tuple(evaluate_consistent(imgL, imgR, scored, sure, args.path_disp_gt, args.flip))))
     if args.encode or args.error_map:
         # kitti16 / u8 mark what the check rejects as invalid; a filled map has no such pixel
-        encode_outputs(disp, out, args.encode, args.vrange, None if args.fill else mask, args.path_disp_gt,
-                       args.error_map)
+        encode_outputs(disp, out, args.encode, args.vrange, None if args.fill else (keep if mask is None else mask),
+                       args.path_disp_gt, args.error_map)
     if args.encode:
         pass
     elif out.endswith(".pfm"):

@@ -55,7 +55,29 @@ def predict_confidence(model, imL, imR, radius=4):
     return res
 
 
-def left_right_check(model, imL, imR, threshold=1.0, fill=True):
+def _speckle_pair(speckle):
+    """``speckle=(max_size, max_diff)`` of the entry points, checked: (int, float)."""
+    try:
+        max_size, max_diff = speckle
+    except (TypeError, ValueError):
+        raise ValueError("speckle is a pair (max_size, max_diff), got %r" % (speckle,))
+    return max_size, max_diff
+
+
+def remove_speckles(disp, max_size, max_diff, valid=None):
+    """One map with its speckles removed: ``(out, keep)`` of ``costvolume.filter_speckles``.
+
+    A speckle is a connected region of at most ``max_size`` pixels: 4-neighbours are joined where both are
+    finite (and allowed by ``valid``, if given) and differ by at most ``max_diff`` in float32 -- OpenCV's
+    ``filterSpeckles(img, 0, max_size, max_diff)``.  ``disp``: (B,1,H,W) or (B,H,W) float32 on the device;
+    ``valid``: the same shape, ``torch.bool`` or ``torch.uint8``.  ``out`` is ``disp`` with the removed
+    pixels (and those that were not finite or not valid) set to 0, ``keep`` the ``torch.bool`` mask of what
+    stayed -- what ``fill_background`` and ``encode_disparity`` take as their mask.  No host read; capturable."""
+    r = cv.filter_speckles(disp, max_size, max_diff, valid=valid, new_val=0.0, want=("out", "keep"))
+    return r.out, r.keep
+
+
+def left_right_check(model, imL, imR, threshold=1.0, fill=True, speckle=None):
     """Both views' disparity, consistency mask and weight, and the filled maps, of one batch.
 
     ``model``: a network of the factory (``forward(imL, imR) -> (_, [disp, ...])``, the first map (B,1,H,W)
@@ -69,9 +91,18 @@ def left_right_check(model, imL, imR, threshold=1.0, fill=True):
       maskL, maskR      ``torch.bool``: |d - warped other view| < ``threshold`` and the sample inside
       weightL, weightR  the reference's soft weight (loss.py:393-404), factor 1
       filledL, filledR  with ``fill``: the maps with the rejected pixels filled from the background
-    The right view is checked in the mirrored frame (loss.py:452) and its results are flipped back."""
+    The right view is checked in the mirrored frame (loss.py:452) and its results are flipped back.
+
+    ``speckle=(max_size, max_diff)``: after the check each view's map goes through
+    ``costvolume.filter_speckles`` with ``valid=`` its check mask (the right view in the mirrored frame,
+    like the rest), so that an island of at most ``max_size`` pixels that passed the check by accident
+    does not decide the fill of its row.  The result gains
+      keepL, keepR      ``torch.bool``: passed the check and lies in a region of more than ``max_size`` pixels
+    and ``filledL`` / ``filledR`` are filled from ``keep``; ``maskL`` / ``maskR`` stay the check's own."""
     flip = lambda t: torch.flip(t, dims=[-1])
     want = ("weight", "mask")
+    if speckle is not None:
+        max_size, max_diff = _speckle_pair(speckle)
     model.eval()
     with torch.no_grad(), cv.amax_scope(imL.device):
         out = model(imL, imR)
@@ -86,7 +117,12 @@ def left_right_check(model, imL, imR, threshold=1.0, fill=True):
         right = cv.lr_check(dRm, dL, mirrored=True, threshold=threshold, want=want)
         res = {"dispL": dL, "dispR": flip(dRm), "maskL": left.mask, "maskR": flip(right.mask),
                "weightL": left.weight, "weightR": flip(right.weight)}
+        okL, okR = left.mask, right.mask
+        if speckle is not None:
+            okL = cv.filter_speckles(dL, max_size, max_diff, valid=left.mask, want=("keep",)).keep
+            okR = cv.filter_speckles(dRm, max_size, max_diff, valid=right.mask, want=("keep",)).keep
+            res["keepL"], res["keepR"] = okL, flip(okR)
         if fill:
-            res["filledL"] = cv.fill_background(dL, left.mask)
-            res["filledR"] = flip(cv.fill_background(dRm, right.mask))
+            res["filledL"] = cv.fill_background(dL, okL)
+            res["filledR"] = flip(cv.fill_background(dRm, okR))
     return res

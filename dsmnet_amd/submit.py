@@ -175,7 +175,7 @@ def _pad_sizes(H, W, multiple):
 
 
 def submit(model, dataset, dirpath_save, batch_size=1, pad_multiple=None, formats=("u16",), vrange=None,
-           lr_check=False, augment=transforms.Stereo_normalize(), threads=4):
+           lr_check=False, augment=transforms.Stereo_normalize(), threads=4, speckle=None):
     """Every file of ``dataset`` through ``model``; results under ``dirpath_save`` as the module text says.
 
     ``dataset``: a ``Dataset_stereo`` (``dataset_stereo_by_name(..., Train=False)``); its transform is not
@@ -186,7 +186,10 @@ def submit(model, dataset, dirpath_save, batch_size=1, pad_multiple=None, format
     With ground truth (a 7-channel dataset) each file's D1 / EPE come from ``costvolume.stereo_metrics``
     over the un-padded map, one host read per batch.  ``vrange``: viridis' fixed range; None: each image's
     own.  ``lr_check=True``: both views are predicted (``postprocess.left_right_check``) and the pixels the
-    check rejects are 0 in ``u16`` and ``u8`` and black in the pictures.
+    check rejects are 0 in ``u16`` and ``u8`` and black in the pictures.  ``speckle=(max_size, max_diff)``:
+    the connected regions of at most ``max_size`` pixels (``costvolume.filter_speckles``) are rejected in the
+    same way -- alone, of the predicted map; with ``lr_check``, among the consistent pixels
+    (``left_right_check(speckle=)``).  The regions are those of the frame the network saw, padding included.
 
     When ``<dirpath_save>.pkl`` exists, its lines are printed and nothing runs (stereo.py:124-137).
     Returns the saved dict.  ``time``: the wall time of the file's batch, loading included, over its size."""
@@ -221,11 +224,14 @@ def submit(model, dataset, dirpath_save, batch_size=1, pad_multiple=None, format
             with torch.no_grad():
                 if lr_check:
                     from .postprocess import left_right_check
-                    res = left_right_check(model, seen[:, :3].contiguous(), seen[:, 3:6].contiguous(), fill=False)
-                    disp, mask = res["dispL"], res["maskL"]
+                    res = left_right_check(model, seen[:, :3].contiguous(), seen[:, 3:6].contiguous(), fill=False,
+                                           speckle=speckle)
+                    disp, mask = res["dispL"], res["maskL" if speckle is None else "keepL"]
                 else:
                     with cv.amax_scope(batch.device):
                         disp = model(seen[:, :3], seen[:, 3:6])[1][0]
+                    if speckle is not None:
+                        mask = cv.filter_speckles(disp, speckle[0], speckle[1], want=("keep",)).keep
                 gt_frame = gt
                 if gt is not None and (up or right) and "err" in want:
                     gt_frame = torch.nn.functional.pad(gt, (0, right, up, 0))
@@ -279,15 +285,19 @@ def build_parser():
     ap.add_argument("--batch_size", default=1, type=int)
     ap.add_argument("--pad_multiple", default=64, type=int, help="pad top / right to multiples of this (0: no padding)")
     ap.add_argument("--lr_check", action="store_true", help="predict both views and zero the inconsistent pixels")
+    ap.add_argument("--speckle", nargs=2, type=float, default=None, metavar=("SIZE", "DIFF"),
+                    help="zero the connected regions of at most SIZE pixels, neighbours joined where they differ by at "
+                         "most DIFF (OpenCV's filterSpeckles); with --lr_check among the consistent pixels")
     ap.add_argument("--threads", default=4, type=int, help="decoding and PNG-writing threads (at most 16)")
     return ap
 
 
 def main(argv=None):
     from .datasets import dataset_stereo_by_name
-    from .deploy import load_weights
+    from .deploy import load_weights, speckle_args
     from .models import model_create_by_name
     args = build_parser().parse_args(argv)
+    speckle = speckle_args(args.speckle)
     if not torch.cuda.is_available():
         raise SystemExit("dsmnet_amd.submit needs an MI355X: the HIP path has no CPU fallback")
     out = args.out or os.path.join("submit", "%s_%s" % (args.dataset, args.net))
@@ -295,7 +305,8 @@ def main(argv=None):
     model = model_create_by_name(args.net, args.maxdisparity)
     load_weights(model, args.path_weight)
     submit(model.eval().cuda(), dataset, out, batch_size=args.batch_size, pad_multiple=args.pad_multiple or None,
-           formats=tuple(args.format or ("u16",)), vrange=args.vrange, lr_check=args.lr_check, threads=args.threads)
+           formats=tuple(args.format or ("u16",)), vrange=args.vrange, lr_check=args.lr_check, threads=args.threads,
+           speckle=speckle)
     return out
 
 

@@ -829,6 +829,45 @@ size_t dsm_fill_background_workspace_bytes(int B, int H, int W);
 int dsm_fill_background(const void* disp, const void* mask, void* out, void* workspace, int B, int H, int W,
                         dsm_stream_t stream);
 
+/* (ABI v7, additive) Speckle filter of a disparity map (csrc/speckle.hip): the connected regions of the map
+ * and the removal of the small ones, OpenCV's filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on the
+ * device.  disp (B,H,W) fp32 contiguous (a (B,1,H,W) map is the same memory); valid (B,H,W) uint8, non-zero =
+ * valid, or NULL.  Exact, no tolerance:
+ *    node    a pixel whose disp is finite and which valid (if given) allows.  The value of any other pixel
+ *            is never used.
+ *    edge    two 4-neighbours of one image, both nodes, with fabsf(disp[p] - disp[q]) <= max_diff in fp32.
+ *            Images of a batch are never joined.
+ *    region  a connected component of that graph (transitive: a ramp of steps <= max_diff is one region).
+ *    size    (B,H,W) int32: the number of nodes of the pixel's region, 0 for a pixel that is no node
+ *    keep    (B,H,W) uint8: 1 where the pixel is a node and size > max_size, else 0 (a region is a speckle
+ *            iff size <= max_size; max_size = 0 removes nothing but the pixels that are no nodes)
+ *    out     (B,H,W) fp32: disp where keep, else new_val.  out may be disp itself.
+ * Each of out, keep, size may be NULL, not all three.  Three or four launches on `stream` (tile labelling in
+ * LDS, union across tile borders, flatten and count, apply), integer atomics only: the results do not depend
+ * on the order of execution, two runs give the same bits.  No host synchronisation, capturable, a linear chain.
+ * workspace: dsm_speckle_workspace_bytes(B, H, W) bytes = B * H * W * 8 (0 for non-positive sizes): an int32
+ * label and an int32 count per pixel, every byte written by the first launch before anything reads it.
+ * DSM_ERR_ARG (nothing launched): NULL args, disp or workspace; all three outputs NULL; B, H or W < 1;
+ * max_size < 0; max_diff negative, NaN or infinite; flags != 0.  DSM_ERR_ALIGN: disp, out, size or workspace
+ * not 4-byte aligned (nothing beyond the types' own alignment is asked for).  DSM_ERR_UNSUPPORTED:
+ * B * H * W >= 2^31 (int32 linear indices).  sizeof(dsm_speckle_args) == 80. */
+typedef struct dsm_speckle_args {
+  const void* disp;
+  const void* valid;
+  void* out;
+  void* keep;
+  void* size;
+  void* workspace;
+  int B, H, W;
+  int max_size;
+  float max_diff;
+  float new_val;
+  int flags;
+} dsm_speckle_args;
+
+size_t dsm_speckle_workspace_bytes(int B, int H, int W);
+int dsm_speckle_filter(const dsm_speckle_args* args, dsm_stream_t stream);
+
 /* (ABI v7, additive) Result maps of a disparity map (csrc/encode.hip), the inverse of dsm_stereo_spatial_raw:
  * from the fp32 map to the bytes of the files a user keeps.  One launch; two with DSM_ENCODE_AUTO_RANGE.  No
  * atomics, no host synchronisation, capturable.
